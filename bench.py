@@ -15,8 +15,15 @@ buffer over RCCL: a reduce-scatter of the fields group (Adam on the rank's 1/W s
 16-bit working copy) plus, on update steps, an all-reduce of the proposal / pose ranges
 (nerf_vo_amd/parallel.py; NVO_SHARD_OPT=0: one all-reduce, replicated Adam).
 
-Extra JSON objects: "roofline" (dominant kernel, live HIP-event timing) and "cpu_baseline" (the
-torch-CPU oracle of the same step on a bounded sample, rank 0 / N=1 only).
+A plain run sets up, warms up, times the K steps and prints the result line.  Everything else the benchmark
+measures runs only with --full: the eager per-kernel table and its "roofline" objects (live PMC passes included),
+the late-schedule window, full-image renders, the occupancy-grid back-end, "cpu_baseline" (the torch-CPU oracle of
+the same step on a bounded sample), the whole mapping loop and render PSNR.
+
+--dump-outputs DIR (single GPU) replays DUMP_REPLAY_STEPS step(s) of the timed path on a fresh engine after the timing
+-- seeded initial parameters, seeded rays -- and writes what the last one hands its caller (rendered rays, loss terms) as
+DIR/<name>.npy.  The rendered rays are the same bit for bit in every run, the loss terms to the order of their
+float-atomic shards, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -88,6 +95,30 @@ def algorithmic_bytes(name: str, cfg, R: int, fused_adam_params: int = 0) -> flo
     if name == "adam":
         return None  # several launches of different sizes: priced from the parameter count below
     return None
+
+
+DUMP_MAX_ROWS = 1 << 20  # per dumped array: a larger one is written as a fixed, seeded sample of this many rows
+# --dump-outputs: steps replayed from the seeded state, the last one written.  One: after a second step the rendered rays
+# already differ between runs by 1e-5 relative (Adam sign flips of the first step's near-cancelling gradients).
+DUMP_REPLAY_STEPS = 1
+
+
+def dump_outputs(out_dir: str, engine, R: int) -> None:
+    """--dump-outputs: what a training step hands its caller -- the rendered outputs of the step's R rays (float32) and
+    its loss terms (float64, engine.loss_totals order) -- as out_dir/<name>.npy.  An array of more than DUMP_MAX_ROWS
+    rows is sampled with a fixed seed, so two builds write the same rows and the dump stays below 64 MB."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    ws = engine._workspace(R, True)
+    arrays = {"rgb": ws["out_rgb"][:R], "depth": ws["out_depth"][:R], "expected_depth": ws["out_expected_depth"][:R],
+              "accumulation": ws["out_accumulation"][:R]}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.shape[0] > DUMP_MAX_ROWS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_MAX_ROWS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    np.save(os.path.join(out_dir, "losses.npy"), engine.loss_totals().double().cpu().numpy())
 
 
 def pmc_traffic(name: str, live_path: str | None = None):
@@ -332,6 +363,13 @@ def main() -> None:
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--mlp-dtype", choices=("f16", "bf16"), default=None)
     ap.add_argument("--rays", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the timed steps (per-kernel table and roofline, late schedule, "
+                         "renders, occupancy-grid back-end, CPU baseline, mapping loop, render PSNR); the options below "
+                         "that configure those sections take effect only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timing, replay DUMP_REPLAY_STEPS steps of the timed path on a fresh engine (seeded "
+                         "parameters and rays) and write the last one's rendered rays and losses as DIR/<name>.npy; single GPU")
     ap.add_argument("--cpu-baseline", choices=("configs0", "sample", "off"), default="configs0",
                     help="configs0 = BASELINE configs[0] as written: one 640x480 keyframe, 4096 rays, fp32 torch-CPU, calibrated "
                          "thread count, median of 20 timed steps after 3 warm-ups (about 1 min of CPU); sample = 256-ray sample (about 12 s)")
@@ -384,6 +422,8 @@ def main() -> None:
     ap.add_argument("--pipeline-single-gpu", action="store_true",
                     help="run the next step's sampling prefix beside the fields Adam inside this step's graph (A/B; measured neutral)")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs runs on a single GPU (--gpus 1)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher -- it never touches a GPU
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -509,14 +549,14 @@ def main() -> None:
 
     use_graph = not args.no_graph
 
-    def step():
+    def step(eng=engine):
         nonlocal use_graph
         if use_graph:
-            engine.train_step_graphed(ds, all_reduce=reducer)
+            eng.train_step_graphed(ds, all_reduce=reducer)
         else:
-            ray_indices, _ = dm.next_train(engine.step)
-            engine.train_step(ray_indices, intr, c2w, ds.frames_color, ds.frames_depth, all_reduce=reducer,
-                              normals=ds.world_normals01() if use_normals else None)
+            ray_indices, _ = dm.next_train(eng.step)
+            eng.train_step(ray_indices, intr, c2w, ds.frames_color, ds.frames_depth, all_reduce=reducer,
+                           normals=ds.world_normals01() if use_normals else None)
 
     def fence():
         torch.cuda.synchronize(device)
@@ -539,6 +579,18 @@ def main() -> None:
     ms_per_step = elapsed / args.steps * 1e3
     samples_per_step = args.rays * cfg.num_nerf_samples * world
     value = samples_per_step / (elapsed / args.steps)
+    if args.dump_outputs:
+        # The timed steps sum gradients in float atomics whose order changes from run to run, and Adam (eps 1e-15) turns
+        # that order noise in near-zero gradients into full-size updates: the timed engine's own last step differs
+        # between two runs of one build far beyond rounding (EXPERIMENTS.md 11.1).  The dump replays DUMP_REPLAY_STEPS
+        # step(s) of the same timed path on a fresh engine, from the seeded initial parameters and the seeded rays, and
+        # writes the last one.  (The engine stays alive to the end: dropping step graphs breaks later captures,
+        # EXPERIMENTS.md 10.11.)
+        dump_engine = NerfactoEngine(cfg, device, world_size=world, rank=rank)
+        for _ in range(DUMP_REPLAY_STEPS):
+            step(dump_engine)
+        fence()
+        dump_outputs(args.dump_outputs, dump_engine, args.rays)
     losses = engine.loss_dict()
 
     # ---- roofline: same K steps again with per-launch HIP events on the launch stream
@@ -546,7 +598,7 @@ def main() -> None:
     live_summary_path = None
     kernel_table = []
     lib = _lib.lib()
-    prof_steps = 0 if args.no_kernel_table else min(args.steps, 50)
+    prof_steps = 0 if (args.no_kernel_table or not args.full) else min(args.steps, 50)
     if rank == 0 and prof_steps:
         lib.nvo_profile_enable(1)
     fence()
@@ -561,7 +613,7 @@ def main() -> None:
     # about one step's host time at the head of every profiled step lets the host run ahead: the scopes then see
     # their kernels back to back, which is what rocprofv3's per-kernel durations add up to.
     spin_cycles = 0
-    if hasattr(torch.cuda, "_sleep"):
+    if prof_steps and hasattr(torch.cuda, "_sleep"):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda._sleep(1_000_000)
         torch.cuda.synchronize(device)
@@ -664,7 +716,7 @@ def main() -> None:
     # [warmup, warmup + K) of a fresh run, where nerfacto refreshes its proposal networks every 2nd step; past the
     # 5000-step proposal warm-up they are refreshed every 6th step (the reference trains 8192 steps per sequence).
     late = None
-    if args.late_steps > 0:
+    if args.full and args.late_steps > 0:
         engine.step = 6000
         for _ in range(12):
             step()
@@ -687,7 +739,7 @@ def main() -> None:
     # Replica: evaluation_frame_* keys absent, /root/reference/run.py:57-66) and at the training resolution, chunks of
     # 32 768 rays (nerfstudio's eval_num_rays_per_chunk), one hipGraph per image, inputs already on the device
     render = None
-    if rank == 0 and world == 1 and args.render_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.render_frames > 0:
         from nerf_vo_amd.mapping.cameras import Cameras
         from nerf_vo_amd.synthetic import replica_intrinsics
 
@@ -773,7 +825,7 @@ def main() -> None:
     # ---- the occupancy-grid ("instant-ngp") back-end of the same hot path (SURVEY.md section 8 row a13;
     # /root/reference/nerf_vo/mapping/instant_ngp.py:104-105 -> Testbed.frame()): step time through the pyngp facade
     ngp = None
-    if rank == 0 and world == 1 and args.ngp_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.ngp_steps > 0:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import ngp_bench
 
@@ -785,7 +837,7 @@ def main() -> None:
 
     # ---- CPU baseline: the torch-CPU oracle of the same step on a bounded sample (rank 0, N=1)
     cpu_baseline = None
-    if rank == 0 and world == 1 and args.cpu_baseline != "off":
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline != "off":
         from oracle.bench_cpu import time_cpu_step
 
         if args.cpu_baseline == "configs0":  # BASELINE configs[0] as written
@@ -798,7 +850,7 @@ def main() -> None:
     # ---- the reference's whole mapping run (BASELINE configs[1]: "full mapping loop"): MappingModule.step -> Nerfstudio(update |
     # train), 8192 iterations with the ingest cadence, default (non-deterministic) kernels, fixed exact poses
     mapping_loop = None
-    if rank == 0 and world == 1 and args.mapping_loop == "on" and args.workload in ("replica", "replica360"):
+    if args.full and rank == 0 and world == 1 and args.mapping_loop == "on" and args.workload in ("replica", "replica360"):
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import mapping_loop as mapping_loop_mod
 
@@ -811,7 +863,7 @@ def main() -> None:
     # ground-truth poses carried into the model's world, JPEG / 16-bit PNG files, the reference's metrics --
     # /root/reference/evaluation/renderer.py:79-124,239-298, evaluator.py:88-146)
     render_psnr = None
-    if rank == 0 and world == 1 and args.psnr != "off" and args.workload == "replica":
+    if args.full and rank == 0 and world == 1 and args.psnr != "off" and args.workload == "replica":
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         from eval_protocol import run as run_protocol
 

@@ -23,6 +23,10 @@ import ast
 import os
 import tempfile
 
+# MKL's reproducible code path (read when MKL initialises, so before torch loads): the two float32 solves then give the
+# same bits on every x86 host, Intel or AMD, and tests/test_dataset_golden_cpu.py checks the mirror on that same path
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")
+
 import numpy as np
 import torch
 

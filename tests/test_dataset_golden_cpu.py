@@ -5,8 +5,13 @@ not needed here).  Rows a2 / a15 of SURVEY.md section 8: pinned by the reference
 
 Bit-for-bit on the CPU: ingest is indexing, permutes and two small linear solves -- the mirror issues the same torch
 calls on the same values, so every buffer, the normalisation matrix, the solved normal images and the saved dataset file
-must be identical to the last bit."""
+must be identical to the last bit.  The float32 solves go through MKL, whose default code path depends on the host CPU
+(Intel and AMD hosts differ in the last bit); the vectors were made on MKL's reproducible path (MKL_CBWR=COMPATIBLE), and
+the check runs in a child process set to that path, since MKL reads the setting once, when it initialises."""
 import os
+import subprocess
+import sys
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -27,6 +32,14 @@ def _same(a: torch.Tensor, ref: np.ndarray) -> bool:
 
 @pytest.mark.parametrize("schedule,normals", CASES, ids=[f"{s}-normals{n}" for s, n in CASES])
 def test_ingest_matches_the_reference_bit_for_bit(schedule, normals, tmp_path):
+    env = dict(os.environ, MKL_CBWR="COMPATIBLE")
+    res = subprocess.run([sys.executable, os.path.abspath(__file__), schedule, str(normals), str(tmp_path)], env=env,
+                         capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    assert res.stdout.strip().endswith("ingest matches the reference bit for bit"), res.stdout[-2000:]
+
+
+def _check_ingest(schedule, normals, tmp_path):
     from nerf_vo_amd.mapping.dataset import DynamicDataset
 
     g = np.load(GOLDEN)
@@ -62,3 +75,9 @@ def test_ingest_matches_the_reference_bit_for_bit(schedule, normals, tmp_path):
     assert again.num_active_frames == ds.num_active_frames
     assert torch.equal(again.frames_color[: ds.num_active_frames], ds.frames_color[: ds.num_active_frames])
     assert torch.equal(again.camera_extrinsics[: ds.num_active_frames], ds.camera_extrinsics[: ds.num_active_frames])
+
+
+if __name__ == "__main__":  # (the child process of the test above)
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    _check_ingest(sys.argv[1], int(sys.argv[2]), Path(sys.argv[3]))
+    print("ingest matches the reference bit for bit")

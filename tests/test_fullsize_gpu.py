@@ -300,3 +300,34 @@ def test_graphed_step_at_full_size(device, name):
     torch.cuda.synchronize()
     assert not torch.equal(s0, eng.dev_scalars) and bool(torch.isfinite(eng.params).all())
     assert all(np.isfinite(v) for v in eng.loss_dict().values()) and int(eng.skip_flag.sum()) == 0
+
+
+def test_bench_dump_outputs_on_the_gpu(device, tmp_path):
+    """`bench.py --gpus 1 --dump-outputs DIR` as a caller runs it, twice: the result line still reports the timed steps,
+    every dumped array is finite with the step's shape, and the rendered rays of the replayed step are the same bit for
+    bit in both runs (the losses to the order of their float-atomic shards)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "NVO_BENCH_DRY")}
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600, cwd=root)
+        assert res.returncode == 0, res.stderr[-3000:]
+        line = json.loads(res.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        dumps.append({n[:-4]: np.load(out / n) for n in sorted(os.listdir(out))})
+    a, b = dumps
+    assert sorted(a) == ["accumulation", "depth", "expected_depth", "losses", "rgb"]
+    assert a["rgb"].shape == (R, 3) and all(a[n].shape == (R,) for n in ("depth", "expected_depth", "accumulation"))
+    for n, v in a.items():
+        assert np.isfinite(v).all(), n
+    assert a["losses"][0] > 0, "the replayed step carries no colour loss"
+    for n in ("rgb", "depth", "expected_depth", "accumulation"):
+        assert np.array_equal(a[n], b[n]), f"{n} differs between two runs with the same arguments"
+    np.testing.assert_allclose(a["losses"], b["losses"], rtol=1e-5, atol=1e-12)

@@ -205,3 +205,47 @@ def test_bench_names_the_error_when_the_node_has_too_few_gpus(tmp_path):
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "64"], capture_output=True, text=True,
                          env=env, timeout=300, cwd=str(tmp_path))
     assert res.returncode == 3 and "not-enough-gpus" in res.stderr and res.stdout.strip() == ""
+
+
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """`bench.py --dump-outputs DIR`: the step's rendered rays as float32 and its loss terms as float64, whole up to
+    DUMP_MAX_ROWS rows, a larger ray batch as the SAME seeded sample on every call, the dump below 64 MB."""
+    import os
+    import sys
+
+    import numpy as np
+    import torch
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+
+    for R in (256, bench.DUMP_MAX_ROWS + 4096):
+        class Engine:  # the attributes dump_outputs reads
+            ws = {"out_rgb": torch.rand(R, 3), "out_depth": torch.rand(R), "out_expected_depth": torch.rand(R),
+                  "out_accumulation": torch.rand(R)}
+
+            def _workspace(self, R_, training):
+                assert R_ == R and training
+                return self.ws
+
+            def loss_totals(self):
+                return torch.arange(8, dtype=torch.float32)
+
+        eng = Engine()
+        for d in ("a", "b"):
+            bench.dump_outputs(str(tmp_path / f"{R}{d}"), eng, R)
+        names = sorted(os.listdir(tmp_path / f"{R}a"))
+        assert names == sorted(f"{n}.npy" for n in ("rgb", "depth", "expected_depth", "accumulation", "losses"))
+        total = 0
+        for n in names:
+            a, b = np.load(tmp_path / f"{R}a" / n), np.load(tmp_path / f"{R}b" / n)
+            assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+            total += os.path.getsize(tmp_path / f"{R}a" / n)
+        rgb = np.load(tmp_path / f"{R}a" / "rgb.npy")
+        if R <= bench.DUMP_MAX_ROWS:
+            assert np.array_equal(rgb, eng.ws["out_rgb"].numpy())
+        else:
+            assert rgb.shape == (bench.DUMP_MAX_ROWS, 3) and np.isin(rgb[:, 0], eng.ws["out_rgb"][:, 0].numpy()).all()
+        assert np.load(tmp_path / f"{R}a" / "losses.npy").dtype == np.float64
+        assert total < 64 << 20

@@ -18,12 +18,12 @@ PY
 }
 case $STAGE in
 bench)   # the driver's own command, every section
-    python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${R}_bench_n1_driver_style.json 2> $OUT/${R}_bench_n1_driver_style.err
+    python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/${R}_bench_n1_driver_style.json 2> $OUT/${R}_bench_n1_driver_style.err
     grep "^\[bench\]" $OUT/${R}_bench_n1_driver_style.err > $OUT/${R}_bench_n1_driver_style_kernel_table.txt
     cp $OUT/live_pmc_fetch_write_per_kernel.json $OUT/${R}_pmc_fetch_write_per_kernel.json 2>/dev/null
     line $OUT/${R}_bench_n1_driver_style.json ;;
 variants)
-    run() { name=$1; shift; python3 $ROOT/bench.py $QUIET "$@" > $OUT/${R}_bench_$name.json 2> $OUT/${R}_bench_$name.err
+    run() { name=$1; shift; python3 $ROOT/bench.py --full $QUIET "$@" > $OUT/${R}_bench_$name.json 2> $OUT/${R}_bench_$name.err
             grep "^\[bench\]" $OUT/${R}_bench_$name.err > $OUT/${R}_bench_${name}_kernel_table.txt; line $OUT/${R}_bench_$name.json; }
     run n1 --steps 200 --warmup 20
     run n1_optimize_poses --steps 20 --warmup 5 --optimize-poses

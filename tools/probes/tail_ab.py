@@ -6,7 +6,7 @@ import sys
 
 sys.path.insert(0, ".")
 mode = sys.argv[1]
-sys.argv = ["bench.py"] + sys.argv[2:]
+sys.argv = ["bench.py", "--full"] + sys.argv[2:]  # (the ngp section runs only with --full)
 if mode == "off":
     import nerf_vo_amd.ngp_engine as n
 
