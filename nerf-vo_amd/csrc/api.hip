@@ -516,7 +516,9 @@ struct GridModule : nvo_module_s {
             return NVO_OK;
         }
         if (!strcmp(key, "grid_fwd_small_form")) {
-            NVO_REQUIRE(value >= -1 && value <= 4, "grid_fwd_small_form: -1 (default) or 0..4");
+            NVO_REQUIRE(value == -1 || value == 0 || value == 1 || value == 4,
+                        "grid_fwd_small_form: -1 (default), 0 (generic kernel), 1 (plain) or 4 (instruction-lean); got %lld",
+                        (long long)value);
             fwd_small_form = (int)value;
             return NVO_OK;
         }
@@ -874,9 +876,8 @@ struct NwieModule : nvo_module_s {
         }
         // the encoding's 32-bit accumulators (slice-owner items) scale by the L1 norm of dL/d(encoded): the network's
         // backward sums it while it stores those values -- no pass of its own over them
-        static const bool l1_from_mlp = [] { const char* e = getenv("NVO_GRID_L1_FROM_MLP"); return !e || atoi(e) != 0; }();
         const NvoGridSlices* owner = enc->bwd_mode == 1 ? &enc->slices : enc->bwd_mode == 3 ? &enc->stream_bins.owner : nullptr;
-        const bool want_l1 = l1_from_mlp && dparams && owner && owner->acc_bits == 32;
+        const bool want_l1 = dparams && owner && owner->acc_bits == 32;
         const uint32_t l1_blocks = want_l1 ? nvo_mlp_bwd_blocks(net->in_pad, net->width, net->n_hidden, B) : 0u;
         if (want_l1) {
             const size_t bytes = sizeof(float) * (size_t)l1_blocks * (net->in_pad + 1);
@@ -895,8 +896,7 @@ struct NwieModule : nvo_module_s {
             if (want_l1) {
                 owner->ext_l1 = a.dx_l1_partial;
                 owner->ext_live = a.dx_live_partial;
-                static const bool live_dout = [] { const char* e = getenv("NVO_LIVE_FROM_DOUT"); return !e || atoi(e) != 0; }();  // A/B
-                owner->ext_dout = (live_dout && compact_out && a.dx_live_partial) ? reinterpret_cast<const uint16_t*>(dout) : nullptr;
+                owner->ext_dout = (compact_out && a.dx_live_partial) ? reinterpret_cast<const uint16_t*>(dout) : nullptr;
                 owner->ext_blocks = l1_blocks;
                 owner->ext_l1_stride = (uint32_t)net->in_pad;
             }

@@ -1,7 +1,7 @@
 // Multi-resolution hash-grid encoding for gfx950: forward gather, parameter-gradient scatter and
 // input-gradient kernels.  Replaces tiny-cuda-nn's kernel_grid / kernel_grid_backward /
 // kernel_grid_backward_input (upstream grid.h is not vendored in
-// /root/reference, the arithmetic is restated in oracle/grid.py + oracle/c/nvo_oracle.c).
+// the reference tree, the arithmetic is restated in oracle/grid.py + oracle/c/nvo_oracle.c).
 //
 // MI355X design notes
 //  * One thread per (sample, level).  The 1-D grid is mapped so that workgroups that the
@@ -13,19 +13,40 @@
 //    256 contiguous bytes; the fused MLP consumes that layout directly.  The tcnn-API path can ask
 //    for sample-major ("AoS": [N][L] half2) instead.
 //  * Interpolation accumulates in fp32 and rounds once to fp16 (tcnn accumulates in fp16).
-//  * Parameter gradients accumulate in fp32 (tcnn: fp16 atomics for F=2).  Two kernels:
-//      - k_grid_bwd_atomic: global float atomics, lane pairs adjacent on one corner (8 B) so a
-//        wave instruction touches 32 distinct 64-B lines, not 64.
-//      - k_grid_bwd_lds:    "slice owner" scatter -- each workgroup owns a slice of one level's
-//        table in LDS (up to all 160 KiB of the CU), re-derives every sample's corner indices,
-//        accumulates hits with LDS atomics (64-bit fixed point where slices are hit often: LDS
-//        integer atomics run 14x the rate of LDS float atomics on gfx950) and writes the slice back with plain
-//        coalesced stores.  Global atomics on random rows run at ~0.08 TB/s on MI355X
-//        (MI355X_MICROARCH.md, Global float atomics); this path uses none.
+//  * Parameter gradients accumulate in fp32 (tcnn: fp16 atomics for F=2).
+//
+// The kernels of this file, one production path per job (every forward form produces the same bits):
+//  forward (nvo_grid_fwd_launch)
+//      - k_grid_fwd:                 generic, a thread per (sample, level), two samples per thread; either output
+//                                    layout, the indices / dydx outputs.  The main grid's training forward.
+//      - k_grid_fwd_small:           small grids (the proposal networks: 5 levels), the two coarsest levels served from
+//                                    LDS, a thread per sample.  The readable statement of the small-grid arithmetic
+//                                    (option grid_fwd_small_form = 1); the lean forms are pinned to it bit for bit.
+//      - k_grid_fwd_small_lean:      the same, instruction-lean and software-pipelined: the default for small grids.
+//      - k_grid_fwd_runs_lean,
+//        k_grid_fwd_small_runs_lean: run-walking forms (option grid_fwd_runs, inference: a thread walks four consecutive
+//                                    samples and gathers only where the cell changes), with k_grid_fwd_runs and
+//                                    k_grid_fwd_small_runs as the fall-backs for the shapes the lean forms refuse.
+//  backward w.r.t. parameters (grid_bwd_mode)
+//      - k_grid_bwd_atomic (0):      global float atomics, lane pairs adjacent on one corner (8 B) so a wave
+//                                    instruction touches 32 distinct 64-B lines, not 64.
+//      - k_grid_bwd_lds (1):         "slice owner" scatter -- each workgroup owns a slice of one level's table in LDS
+//                                    (up to all 160 KiB of the CU), re-derives every sample's corner indices,
+//                                    accumulates hits with LDS atomics (fixed point where slices are hit often: LDS
+//                                    integer atomics run 14x the rate of LDS float atomics on gfx950) and writes the
+//                                    slice back with plain coalesced stores.  Global atomics on random rows run at
+//                                    ~0.08 TB/s on MI355X; this path uses none.  Helpers: k_dy_l1, k_live_samples.
+//      - k_tl_scatter_p +
+//        k_tl_accumulate_p (3):      tile-local stream -- levels with many bins go through bin-sorted 12-byte pair
+//                                    records and a streaming accumulate into packed 2 x 32-bit LDS sums (optionally with
+//                                    the Adam step fused in); the coarse levels keep slice-owner items.  Helpers:
+//                                    k_live_rows, k_st_zero_p.
+//  backward w.r.t. the input
+//      - k_grid_bwd_input_dydx:      streams the d(out)/d(cell) block a forward with prepare_input_gradients stored.
+//      - k_grid_bwd_input (+ k_sum_levels): gathers the corners again; per-level partials, no float atomics.
 #include "nvo_kernels.h"
 
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -409,7 +430,7 @@ k_grid_fwd_runs(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const 
 // Same fp32 interpolation, same order, one rounding: bit-identical to k_grid_fwd.
 constexpr int kSmallBlock = 1024;
 
-template <int NLDS, int NG, int SPT>
+template <int NLDS, int NG>
 __global__ void __launch_bounds__(kSmallBlock)
 k_grid_fwd_small(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const __half2* __restrict__ table,
                  __half2* __restrict__ out, int out_bf16, uint32_t per_block) {
@@ -430,94 +451,75 @@ k_grid_fwd_small(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const
     const uint32_t first = blockIdx.x * per_block;
     const uint32_t last = min(N, first + per_block);
     uint32_t* __restrict__ o32 = reinterpret_cast<uint32_t*>(out);
-    // SPT samples per thread and pass (kSmallBlock apart: coalescing as with one): with one 1024-thread workgroup per CU
-    // the launch is latency-bound (PMC: waves wait 59 % of their cycles) -- twice the gathers in flight per wave
-    for (uint32_t i0 = first + threadIdx.x; i0 < last; i0 += kSmallBlock * SPT) {
-        uint32_t is[SPT];
-        float pos[SPT][3];
+    for (uint32_t i = first + threadIdx.x; i < last; i += kSmallBlock) {
+        float pos[3];
 #pragma unroll
-        for (int s = 0; s < SPT; ++s) {
-            is[s] = i0 + (uint32_t)s * kSmallBlock;
-            const uint32_t ic = min(is[s], last - 1u);  // (unconditional loads; a sample past the end stores nothing)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) pos[s][k] = x[3 * (size_t)ic + k];
-        }
+        for (int k = 0; k < 3; ++k) pos[k] = x[3 * (size_t)i + k];
         GP_CLK(gfa);
-        // ---- global levels first: every gather of the samples is requested before anything is consumed
-        Corner cg[SPT][NG];
-        uint32_t vg[SPT][NG][8];
+        // ---- global levels first: every gather of the sample is requested before anything is consumed
+        Corner cg[NG];
+        uint32_t vg[NG][8];
 #pragma unroll
-        for (int s = 0; s < SPT; ++s) {
+        for (int q = 0; q < NG; ++q) {
+            const uint32_t level = NLDS + q;
+            const uint32_t off = g.offset[level], size = g.offset[level + 1] - off, res = g.resolution[level];
+            const uint32_t hashed = g.hashed[level];
+            const uint32_t* __restrict__ tl = tab32 + off;
+            cg[q] = grid_cell(g.scale[level], pos[0], pos[1], pos[2]);
 #pragma unroll
-            for (int q = 0; q < NG; ++q) {
-                const uint32_t level = NLDS + q;
-                const uint32_t off = g.offset[level], size = g.offset[level + 1] - off, res = g.resolution[level];
-                const uint32_t hashed = g.hashed[level];
-                const uint32_t* __restrict__ tl = tab32 + off;
-                cg[s][q] = grid_cell(g.scale[level], pos[s][0], pos[s][1], pos[s][2]);
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    const uint32_t cy = cg[s][q].py + (j & 1u), cz = cg[s][q].pz + (j >> 1);
-                    const uint32_t i0c = nvo_grid_index(hashed, size, res, cg[s][q].px, cy, cz);
-                    const uint32_t i1c = nvo_grid_index(hashed, size, res, cg[s][q].px + 1u, cy, cz);
-                    if (hashed ? ((cg[s][q].px & 1u) == 0u) : false) {
-                        // even cell x: idx1 == idx0 ^ 1 -- both corners sit in one aligned 8-byte pair
-                        const uint2 pr = *reinterpret_cast<const uint2*>(tl + (i0c & ~1u));
-                        vg[s][q][2 * j] = (i0c & 1u) ? pr.y : pr.x;
-                        vg[s][q][2 * j + 1] = (i0c & 1u) ? pr.x : pr.y;
-                    } else if (!hashed && i1c == i0c + 1u) {
-                        // dense level: x neighbours are neighbours in memory (dword alignment suffices)
-                        const uint2 pr = nvo_ld_u2_a4(tl + i0c);
-                        vg[s][q][2 * j] = pr.x;
-                        vg[s][q][2 * j + 1] = pr.y;
-                    } else {
-                        vg[s][q][2 * j] = tl[i0c];
-                        vg[s][q][2 * j + 1] = tl[i1c];
-                    }
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t cy = cg[q].py + (j & 1u), cz = cg[q].pz + (j >> 1);
+                const uint32_t i0c = nvo_grid_index(hashed, size, res, cg[q].px, cy, cz);
+                const uint32_t i1c = nvo_grid_index(hashed, size, res, cg[q].px + 1u, cy, cz);
+                if (hashed ? ((cg[q].px & 1u) == 0u) : false) {
+                    // even cell x: idx1 == idx0 ^ 1 -- both corners sit in one aligned 8-byte pair
+                    const uint2 pr = *reinterpret_cast<const uint2*>(tl + (i0c & ~1u));
+                    vg[q][2 * j] = (i0c & 1u) ? pr.y : pr.x;
+                    vg[q][2 * j + 1] = (i0c & 1u) ? pr.x : pr.y;
+                } else if (!hashed && i1c == i0c + 1u) {
+                    // dense level: x neighbours are neighbours in memory (dword alignment suffices)
+                    const uint2 pr = nvo_ld_u2_a4(tl + i0c);
+                    vg[q][2 * j] = pr.x;
+                    vg[q][2 * j + 1] = pr.y;
+                } else {
+                    vg[q][2 * j] = tl[i0c];
+                    vg[q][2 * j + 1] = tl[i1c];
                 }
             }
         }
         GP_CLK(gfb);
         // ---- LDS levels while the gathers fly
 #pragma unroll
-        for (int s = 0; s < SPT; ++s) {
-            if (is[s] >= last) continue;
+        for (int l = 0; l < NLDS; ++l) {
+            const uint32_t off = g.offset[l], size = g.offset[l + 1] - off, res = g.resolution[l];
+            const uint32_t* tl = lds_tab + off;
+            const Corner c = grid_cell(g.scale[l], pos[0], pos[1], pos[2]);
+            float r0 = 0.f, r1 = 0.f;
 #pragma unroll
-            for (int l = 0; l < NLDS; ++l) {
-                const uint32_t off = g.offset[l], size = g.offset[l + 1] - off, res = g.resolution[l];
-                const uint32_t* tl = lds_tab + off;
-                const Corner c = grid_cell(g.scale[l], pos[s][0], pos[s][1], pos[s][2]);
-                float r0 = 0.f, r1 = 0.f;
-#pragma unroll
-                for (uint32_t k = 0; k < 8; ++k) {
-                    const uint32_t idx = nvo_grid_index(0u, size, res, c.px + (k & 1u), c.py + ((k >> 1) & 1u), c.pz + ((k >> 2) & 1u));
-                    const float w = ((k & 1u) ? c.wx : 1.f - c.wx) * ((k & 2u) ? c.wy : 1.f - c.wy) *
-                                    ((k & 4u) ? c.wz : 1.f - c.wz);
-                    const float2 f = __half22float2(__builtin_bit_cast(__half2, tl[idx]));
-                    r0 = fmaf(w, f.x, r0);
-                    r1 = fmaf(w, f.y, r1);
-                }
-                o32[(size_t)l * N + is[s]] = nvo_cvt16x2(r0, r1, out_bf16 != 0);
+            for (uint32_t k = 0; k < 8; ++k) {
+                const uint32_t idx = nvo_grid_index(0u, size, res, c.px + (k & 1u), c.py + ((k >> 1) & 1u), c.pz + ((k >> 2) & 1u));
+                const float w = ((k & 1u) ? c.wx : 1.f - c.wx) * ((k & 2u) ? c.wy : 1.f - c.wy) *
+                                ((k & 4u) ? c.wz : 1.f - c.wz);
+                const float2 f = __half22float2(__builtin_bit_cast(__half2, tl[idx]));
+                r0 = fmaf(w, f.x, r0);
+                r1 = fmaf(w, f.y, r1);
             }
+            o32[(size_t)l * N + i] = nvo_cvt16x2(r0, r1, out_bf16 != 0);
         }
         GP_CLK(gfc);
 #pragma unroll
-        for (int s = 0; s < SPT; ++s) {
-            if (is[s] >= last) continue;
+        for (int q = 0; q < NG; ++q) {
+            const Corner& c = cg[q];
+            float r0 = 0.f, r1 = 0.f;
 #pragma unroll
-            for (int q = 0; q < NG; ++q) {
-                const Corner& c = cg[s][q];
-                float r0 = 0.f, r1 = 0.f;
-#pragma unroll
-                for (uint32_t k = 0; k < 8; ++k) {
-                    const float w = ((k & 1u) ? c.wx : 1.f - c.wx) * ((k & 2u) ? c.wy : 1.f - c.wy) *
-                                    ((k & 4u) ? c.wz : 1.f - c.wz);
-                    const float2 f = __half22float2(__builtin_bit_cast(__half2, vg[s][q][k]));
-                    r0 = fmaf(w, f.x, r0);
-                    r1 = fmaf(w, f.y, r1);
-                }
-                o32[(size_t)(NLDS + q) * N + is[s]] = nvo_cvt16x2(r0, r1, out_bf16 != 0);
+            for (uint32_t k = 0; k < 8; ++k) {
+                const float w = ((k & 1u) ? c.wx : 1.f - c.wx) * ((k & 2u) ? c.wy : 1.f - c.wy) *
+                                ((k & 4u) ? c.wz : 1.f - c.wz);
+                const float2 f = __half22float2(__builtin_bit_cast(__half2, vg[q][k]));
+                r0 = fmaf(w, f.x, r0);
+                r1 = fmaf(w, f.y, r1);
             }
+            o32[(size_t)(NLDS + q) * N + i] = nvo_cvt16x2(r0, r1, out_bf16 != 0);
         }
 #ifdef NVO_GRID_PHASE
         {
@@ -536,161 +538,13 @@ k_grid_fwd_small(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const
 #endif
 }
 
-// k_grid_fwd_small, SOFTWARE-PIPELINED (round 6).  A fit of the two training launches (1 M samples 33 us, 393 K samples
-// 26 us) puts ~22 us of every launch into what does not scale with the samples: the LDS staging ran as ~10 dependent
-// L2 round trips (one 16-byte load -> store per thread and iteration), and every pass of a workgroup exposed its own
-// position load and gather latencies one after the other.  Here (a) all staging loads of a thread are in flight at once
-// (<= kStageMax x 16 bytes in registers), (b) the first pass's positions and global-level gathers are requested BEFORE the
-// staging loads are waited for, (c) pass p + 2's positions and pass p + 1's gathers are in flight while pass p is consumed
-// (loads return in issue order, so each wait only covers what was issued before it).  Same arithmetic, same order, one
-// rounding: bit-identical to k_grid_fwd_small.
+// staging vectors a thread of the lean small-grid forms keeps in flight at once
 constexpr int kStageMax = 10;  // 10 x 16 B x 1024 threads = 160 KiB >= the 152 KiB the launcher admits
 
-template <int NLDS, int NG>
-__global__ void __launch_bounds__(kSmallBlock)
-k_grid_fwd_small_pipe(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const __half2* __restrict__ table,
-                      __half2* __restrict__ out, int out_bf16, uint32_t per_block) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_tab[];
-    const uint32_t* __restrict__ tab32 = reinterpret_cast<const uint32_t*>(table);
-    const uint32_t first = blockIdx.x * per_block;
-    const uint32_t last = min(N, first + per_block);
-    if (first >= last) return;  // (uniform)
-    const uint32_t n_pass = (last - first + kSmallBlock - 1u) / kSmallBlock;
-    uint32_t* __restrict__ o32 = reinterpret_cast<uint32_t*>(out);
-
-    struct Pos { float v[3]; };
-    auto load_pos = [&](uint32_t pass) {  // (unconditional; a slot past the end re-reads the last sample and stores nothing)
-        const uint32_t ic = min(first + pass * kSmallBlock + threadIdx.x, last - 1u);
-        Pos p;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p.v[k] = x[3 * (size_t)ic + k];
-        return p;
-    };
-    // What a gather leaves in registers is consumed a pass later, and NOTHING is computed from a loaded value next to its
-    // load: a select or convert behind a load inside a lane-divergent branch makes the compiler wait for that load right
-    // there (the value must exist at the join), which serialised the twelve gathers of a sample into twelve L2 round trips
-    // in the first form of this kernel.  Per (y, z) pair: `pr` = the aligned 8-byte pair that holds corner x (hashed levels;
-    // on dense levels the 8 bytes at corner x), `ex` = corner x + 1 where `pr` does not hold it -- requested under a
-    // branch that contains the load alone, so only the lanes that need it reach the L1.
-    Corner cg[NG];
-    uint2 pr[NG][4];
-    uint32_t ex[NG][4];
-    uint32_t sel[NG];  // bit j: corner x of pair j is pr.y (hashed, odd index); bit 4 + j: corner x + 1 comes from ex
-    auto issue = [&](const Pos& p) {  // cells of the global levels + every gather of the sample
-        // index arithmetic of ALL pairs first (the dense levels' modulo sits behind a branch), then nothing but loads: a
-        // register written between two loads can collide with an outstanding load's destination and wait for it
-        uint32_t a0[NG][4], a1[NG][4];
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-            const uint32_t level = NLDS + q;
-            const uint32_t off = g.offset[level], size = g.offset[level + 1] - off, res = g.resolution[level];
-            const uint32_t hashed = g.hashed[level];
-            cg[q] = grid_cell(g.scale[level], p.v[0], p.v[1], p.v[2]);
-            sel[q] = 0u;
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                const uint32_t cy = cg[q].py + (j & 1u), cz = cg[q].pz + (j >> 1);
-                const uint32_t i0c = nvo_grid_index(hashed, size, res, cg[q].px, cy, cz);
-                const uint32_t i1c = nvo_grid_index(hashed, size, res, cg[q].px + 1u, cy, cz);
-                // hashed: idx1 == idx0 ^ 1 when the cell's x is even -- both corners in one aligned pair; dense: x neighbours
-                // are neighbours in memory unless the pair straddles the table's wrap (dword alignment suffices; the last
-                // entry's pair would reach past the level: taken one entry lower and read from .y)
-                const bool hi = hashed ? (i0c & 1u) != 0u : (i0c + 1u >= size);
-                const bool extra = hashed ? (cg[q].px & 1u) != 0u : (i1c != i0c + 1u);
-                a0[q][j] = off + (hashed ? (i0c & ~1u) : (hi ? i0c - 1u : i0c));
-                a1[q][j] = off + i1c;
-                sel[q] |= (hi ? 1u : 0u) << j | (extra ? 16u : 0u) << j;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                pr[q][j] = nvo_ld_u2_a4(tab32 + a0[q][j]);
-                ex[q][j] = 0u;
-                if ((sel[q] >> (4u + j)) & 1u) ex[q][j] = tab32[a1[q][j]];
-            }
-        }
-    };
-    auto corner = [&](int q, uint32_t k) -> uint32_t {  // raw half2 of corner k (bit 0: x, bit 1: y, bit 2: z)
-        const uint32_t j = k >> 1;
-        const bool hi = (sel[q] >> j) & 1u, extra = (sel[q] >> (4u + j)) & 1u;
-        if ((k & 1u) == 0u) return hi ? pr[q][j].y : pr[q][j].x;
-        return extra ? ex[q][j] : (hi ? pr[q][j].x : pr[q][j].y);
-    };
-
-    Pos p0 = load_pos(0u);
-    {   // staging: every load of the thread requested before the first is stored
-        const uint32_t n4 = g.offset[NLDS] >> 2;
-        const uint4* __restrict__ src = reinterpret_cast<const uint4*>(table);
-        uint4* dst = reinterpret_cast<uint4*>(lds_tab);
-        uint4 st[kStageMax];
-#pragma unroll
-        for (int k = 0; k < kStageMax; ++k) st[k] = src[min(threadIdx.x + (uint32_t)k * kSmallBlock, n4 - 1u)];
-        issue(p0);  // (the first pass's gathers fly with the staging loads)
-        // (branch-free: a slot past the end re-writes the last vector's own value -- a store under `if (e < n4)` lets the
-        // compiler sink each load into its branch, which is the load -> wait -> store chain this form is there to avoid)
-#pragma unroll
-        for (int k = 0; k < kStageMax; ++k) dst[min(threadIdx.x + (uint32_t)k * kSmallBlock, n4 - 1u)] = st[k];
-    }
-    __syncthreads();
-    for (uint32_t pass = 0; pass < n_pass; ++pass) {
-        const uint32_t i = first + pass * kSmallBlock + threadIdx.x;
-        // (a value carried into the next iteration while its load is still in flight would be waited for at the loop's
-        // register copies together with everything requested after it: the next positions are requested here, have arrived
-        // by the time the gathers have, and only then take p0's place)
-        const Pos p1 = load_pos(min(pass + 1u, n_pass - 1u));
-        const bool live = i < last;
-        // ---- LDS levels while the gathers fly
-        if (live) {
-#pragma unroll
-            for (int l = 0; l < NLDS; ++l) {
-                const uint32_t off = g.offset[l], size = g.offset[l + 1] - off, res = g.resolution[l];
-                const uint32_t* tl = lds_tab + off;
-                const Corner c = grid_cell(g.scale[l], p0.v[0], p0.v[1], p0.v[2]);
-                float r0 = 0.f, r1 = 0.f;
-#pragma unroll
-                for (uint32_t k = 0; k < 8; ++k) {
-                    const uint32_t idx = nvo_grid_index(0u, size, res, c.px + (k & 1u), c.py + ((k >> 1) & 1u), c.pz + ((k >> 2) & 1u));
-                    const float w = ((k & 1u) ? c.wx : 1.f - c.wx) * ((k & 2u) ? c.wy : 1.f - c.wy) *
-                                    ((k & 4u) ? c.wz : 1.f - c.wz);
-                    const float2 f = __half22float2(__builtin_bit_cast(__half2, tl[idx]));
-                    r0 = fmaf(w, f.x, r0);
-                    r1 = fmaf(w, f.y, r1);
-                }
-                o32[(size_t)l * N + i] = nvo_cvt16x2(r0, r1, out_bf16 != 0);
-            }
-        }
-        // ---- consume this pass's gathers
-        uint32_t rg[NG];
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-            const Corner& c = cg[q];
-            float r0 = 0.f, r1 = 0.f;
-#pragma unroll
-            for (uint32_t k = 0; k < 8; ++k) {
-                const float w = ((k & 1u) ? c.wx : 1.f - c.wx) * ((k & 2u) ? c.wy : 1.f - c.wy) *
-                                ((k & 4u) ? c.wz : 1.f - c.wz);
-                const float2 f = __half22float2(__builtin_bit_cast(__half2, corner(q, k)));
-                r0 = fmaf(w, f.x, r0);
-                r1 = fmaf(w, f.y, r1);
-            }
-            rg[q] = nvo_cvt16x2(r0, r1, out_bf16 != 0);
-        }
-        if (live) {
-#pragma unroll
-            for (int q = 0; q < NG; ++q) o32[(size_t)(NLDS + q) * N + i] = rg[q];
-        }
-        // ---- next pass's gathers
-        if (pass + 1u < n_pass) issue(p1);  // (uniform)
-        p0 = p1;
-    }
-}
-
 // k_grid_fwd_small, INSTRUCTION-LEAN (round 6).  The phase clocks (profiles/r6_grid_phase_fwd_small.txt) and an A/B of
-// the pipelined form above against the plain one (no gain with every gather in flight) say what bounds this kernel: not a
-// memory system rate but the vector ALU -- a wave64 instruction occupies its SIMD for 4 cycles (16 for the quarter-rate
-// 32-bit multiplies), four waves share a SIMD, and the first form spent ~900 issue slots per sample on 40 corners: every
+// a software-pipelined form against the plain one (no gain with every gather in flight: EXPERIMENTS.md 10.3, removed in
+// 12.1) say what bounds this kernel: not a memory system rate but the vector ALU -- a wave64 instruction occupies its
+// SIMD for 4 cycles (16 for the quarter-rate 32-bit multiplies), four waves share a SIMD, and the first form spent ~900 issue slots per sample on 40 corners: every
 // corner's index from scratch (v_mad_u64_u32 / v_mul_lo_u32: the compiler neither knows that cell coordinates fit 24
 // bits nor that (py + 1) P = py P + P), 64-bit address arithmetic per load, both index rules compiled into every level
 // and chosen at run time, both 16-bit output formats computed and selected.  Here:
@@ -705,7 +559,9 @@ k_grid_fwd_small_pipe(NvoGridLevels g, uint32_t N, const float* __restrict__ x, 
 //   * corner weights as (wx' wy') wz' exactly as the reference order has them, 12 multiplies per level;
 //   * waves past the workgroup's last sample leave the pass loop, and the workgroups' shares are wave-granular (the
 //     second proposal level's 393 216 samples are 1.5 passes per workgroup: the first form ran 2 on 192 of the 256 CUs);
-//   * the software pipeline of k_grid_fwd_small_pipe (staging loads in flight, next positions / gathers requested early).
+//   * a software pipeline: all staging loads of a thread are in flight at once (<= kStageMax x 16 bytes in registers),
+//     pass p + 2's positions and pass p + 1's gathers are in flight while pass p is consumed (loads return in issue order,
+//     so each wait only covers what was issued before it).
 // Same fp32 interpolation, same order, one rounding: bit-identical to k_grid_fwd_small (tools/probes/fwd_small_ab.py).
 template <bool BF>
 __device__ __forceinline__ uint32_t lean_cvt16x2(float a, float b) {
@@ -770,8 +626,10 @@ k_grid_fwd_small_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, 
         return r;
     };
 
-    // Per global level and (y, z) pair j, what a gather leaves in registers (nothing is computed from a loaded value next to
-    // its load, see k_grid_fwd_small_pipe):
+    // Per global level and (y, z) pair j, what a gather leaves in registers.  It is consumed a pass later, and NOTHING is
+    // computed from a loaded value next to its load: a select or convert behind a load inside a lane-divergent branch makes
+    // the compiler wait for that load right there (the value must exist at the join), which serialises the twelve gathers of
+    // a sample into twelve L2 round trips; a load that only some lanes need sits in a branch that contains the load alone.
     //   hashed level: with pe = px & ~1, the entries of x = pe and x = pe + 1 differ in index bit 0 only -- `pr` = that aligned
     //     8-byte pair (it holds corner px whatever its parity, and corner px + 1 when px is even), `ex` = corner px + 1 when px
     //     is odd.  Which half of the pair is x = pe: bit 0 of the (y, z) hash = (py ^ pz ^ j ^ (j >> 1)) & 1 (both primes are
@@ -850,32 +708,18 @@ k_grid_fwd_small_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, 
         }
     };
 
-#ifndef NVO_LEAN_STAGE
-#define NVO_LEAN_STAGE 1
-#endif
     Pos p0 = load_pos(0u);
-    {   // staging
+    {   // staging: every load of the thread requested before the first is stored.  (Branch-free: a slot past the end
+        // re-writes the last vector's own value -- a store under `if (e < n4)` lets the compiler sink each load into its
+        // branch, which is the load -> wait -> store chain this form is there to avoid.)
         const uint32_t n4 = g.offset[NLDS] >> 2;
         const uint4* __restrict__ src = reinterpret_cast<const uint4*>(table);
         uint4* dst = reinterpret_cast<uint4*>(lds_tab);
-#if NVO_LEAN_STAGE == 0
-        for (uint32_t e = threadIdx.x; e < n4; e += kSmallBlock) dst[e] = src[e];
-#elif NVO_LEAN_STAGE == 2
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            uint4 st[kStageMax / 2];
-#pragma unroll
-            for (int k = 0; k < kStageMax / 2; ++k) st[k] = src[min(threadIdx.x + (uint32_t)(h * (kStageMax / 2) + k) * kSmallBlock, n4 - 1u)];
-#pragma unroll
-            for (int k = 0; k < kStageMax / 2; ++k) dst[min(threadIdx.x + (uint32_t)(h * (kStageMax / 2) + k) * kSmallBlock, n4 - 1u)] = st[k];
-        }
-#else
         uint4 st[kStageMax];
 #pragma unroll
         for (int k = 0; k < kStageMax; ++k) st[k] = src[min(threadIdx.x + (uint32_t)k * kSmallBlock, n4 - 1u)];
 #pragma unroll
         for (int k = 0; k < kStageMax; ++k) dst[min(threadIdx.x + (uint32_t)k * kSmallBlock, n4 - 1u)] = st[k];
-#endif
     }
 #ifdef NVO_GRID_PHASE
     GP_CLK(gls);
@@ -957,167 +801,6 @@ k_grid_fwd_small_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, 
         GP_ADD(32, gl1 - gl0); GP_ADD(33, gl2 - gl1); GP_ADD(37, 1);
     }
 #endif
-}
-
-// k_grid_fwd for the level-major production path, INSTRUCTION-LEAN (round 6): the blockIdx -> (tile, level) plan of
-// k_grid_fwd (XCD-balanced), a thread per (sample, level), SPT samples per thread -- with what k_grid_fwd_small_lean
-// does to the arithmetic: the level's kind is block-uniform and takes one of two straight-line paths; hashed levels
-// compute TWO 32-bit multiplies per sample (the four (y, z) combinations by xor) and fetch the aligned 8-byte pair around
-// corner px plus, for odd px only, corner px + 1 (two lane predicates steer every select) -- one L1 look-up instead of two
-// for half the (y, z) pairs; dense levels one base index from 24-bit multiplies with the generic rule behind a branch;
-// 32-bit byte offsets against scalar bases; packed weight products; the output format a template parameter.
-// Same fp32 interpolation, same order, one rounding: bit-identical to k_grid_fwd.
-template <int SPT, bool BF, bool PAIR>
-__global__ void __launch_bounds__(kGridBlock)
-k_grid_fwd_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const __half2* __restrict__ table,
-                __half2* __restrict__ out, GridFwdPlan plan, const uint32_t* __restrict__ n_live) {
-    uint32_t tile, level;
-    if (plan.enabled) {
-        if (!grid_plan_map(plan, blockIdx.x, &tile, &level)) return;
-    } else {
-        grid_block_map(blockIdx.x, g.n_levels, &tile, &level);
-    }
-    if (n_live && tile * (kGridBlock * SPT) >= *n_live) return;
-    const uint32_t i_first = tile * (kGridBlock * SPT) + threadIdx.x;
-    if (i_first >= N) return;
-    const uint32_t off = g.offset[level];
-    const uint32_t size = g.offset[level + 1] - off;
-    const uint32_t res = g.resolution[level];
-    const uint32_t hashed = g.hashed[level];
-    const float scale = g.scale[level];
-    const unsigned char* __restrict__ tab8 = reinterpret_cast<const unsigned char*>(table + off);  // (the level's base)
-    const unsigned char* __restrict__ x8 = reinterpret_cast<const unsigned char*>(x);
-    unsigned char* __restrict__ o8 = reinterpret_cast<unsigned char*>(out) + (size_t)level * N * 4u;
-
-    // NOTHING below is conditional on a sample being in range: a slot past the end re-reads sample N - 1, computes that
-    // sample's value and stores it to that sample's place (the same bits its owner stores).  A store under `if (i < N)`
-    // lets the compiler sink the slot's index arithmetic AND its gathers into the branch -- behind the previous slot's
-    // consumption -- which halves the gathers in flight (measured: 72 against 59 us on an untrained field's batch).
-    uint32_t i[SPT];
-    Corner c[SPT];
-#pragma unroll
-    for (int s = 0; s < SPT; ++s) {
-        i[s] = i_first + (uint32_t)s * kGridBlock;
-        const float* p = reinterpret_cast<const float*>(x8 + min(i[s], N - 1u) * 12u);
-        const float px = p[0], py = p[1], pz = p[2];
-        c[s] = grid_cell(scale, px, py, pz);
-    }
-    uint2 pr[SPT][4];
-    uint32_t ex[SPT][4];
-    if (hashed) {  // (block-uniform)
-        const uint32_t mask = size - 1u;
-        uint32_t a0[SPT][4], a1[SPT][4];
-#pragma unroll
-        for (int s = 0; s < SPT; ++s) {
-            const uint32_t hy0 = c[s].py * 2654435761u, hy1 = hy0 + 2654435761u;
-            const uint32_t hz0 = c[s].pz * 805459861u, hz1 = hz0 + 805459861u;
-            const uint32_t a[4] = {hy0 ^ hz0, hy1 ^ hz0, hy0 ^ hz1, hy1 ^ hz1};
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                a0[s][j] = ((c[s].px ^ a[j]) & mask & (PAIR ? ~1u : ~0u)) << 2;
-                a1[s][j] = (((c[s].px + 1u) ^ a[j]) & mask) << 2;
-            }
-        }
-        if constexpr (PAIR) {
-            // the aligned 8-byte pair around corner px (+ corner px + 1 for odd px): fewer L1 look-ups, but an 8-byte gather
-            // occupies the address path twice as long as a 4-byte one -- measured SLOWER where the gather binds (60 -> 66 us
-            // on the spread samples of an untrained field, tools/probes/fwd_main_ab.py) and kept for the A/B only
-#pragma unroll
-            for (int s = 0; s < SPT; ++s) {
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    pr[s][j] = *reinterpret_cast<const uint2*>(tab8 + a0[s][j]);
-                    ex[s][j] = 0u;
-                }
-                if (c[s].px & 1u) {  // (the branch holds the four loads alone)
-#pragma unroll
-                    for (uint32_t j = 0; j < 4; ++j) ex[s][j] = *reinterpret_cast<const uint32_t*>(tab8 + a1[s][j]);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int s = 0; s < SPT; ++s) {
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    pr[s][j].x = *reinterpret_cast<const uint32_t*>(tab8 + a0[s][j]);
-                    pr[s][j].y = *reinterpret_cast<const uint32_t*>(tab8 + a1[s][j]);
-                }
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < SPT; ++s) {
-            uint32_t even[4], odd[4];
-            if constexpr (PAIR) {
-                const bool px_odd = (c[s].px & 1u) != 0u;
-                const bool t = (((c[s].py ^ c[s].pz) & 1u) != 0u) != px_odd;  // corner px sits in pr.y for j = 0, 3 (pr.x for 1, 2)
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    const bool hi = (j == 0u || j == 3u) ? t : !t;
-                    even[j] = hi ? pr[s][j].y : pr[s][j].x;
-                    odd[j] = px_odd ? ex[s][j] : (hi ? pr[s][j].x : pr[s][j].y);
-                }
-            } else {
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    even[j] = pr[s][j].x;
-                    odd[j] = pr[s][j].y;
-                }
-            }
-            float w[4][2];
-            lean_weights(c[s], w);
-            *reinterpret_cast<uint32_t*>(o8 + (min(i[s], N - 1u) << 2)) = lean_interp<BF>(w, even, odd);
-        }
-    } else {
-        const uint32_t res2 = res * res;
-        uint32_t a0[SPT][4], a1[SPT][4];
-        bool split[SPT];
-#pragma unroll
-        for (int s = 0; s < SPT; ++s) {
-            const uint32_t base = c[s].px + __umul24(c[s].py, res) + __umul24(c[s].pz, res2);
-            // (24-bit multiplies: exact while coordinates and res^2 stay below 2^24 -- the launcher admits res <= 4096)
-            split[s] = !(max(max(c[s].px, c[s].py), c[s].pz) < res && base + res2 + res + 1u < size);
-            const uint32_t dj[4] = {0u, res, res2, res2 + res};
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                uint32_t i0c = base + dj[j], i1c = i0c + 1u;
-                if (split[s]) {  // the generic rule, corner by corner (upper domain faces; positions outside [0, 1])
-                    const uint32_t cy = c[s].py + (j & 1u), cz = c[s].pz + (j >> 1);
-                    i0c = nvo_grid_index(0u, size, res, c[s].px, cy, cz);
-                    i1c = nvo_grid_index(0u, size, res, c[s].px + 1u, cy, cz);
-                }
-                a0[s][j] = i0c << 2;
-                a1[s][j] = i1c << 2;
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < SPT; ++s) {
-            if (!split[s]) {
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    const NvoU2A4 v = *reinterpret_cast<const NvoU2A4*>(tab8 + a0[s][j]);
-                    pr[s][j] = make_uint2(v.x, v.y);
-                }
-            } else {
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    pr[s][j].x = *reinterpret_cast<const uint32_t*>(tab8 + a0[s][j]);
-                    pr[s][j].y = *reinterpret_cast<const uint32_t*>(tab8 + a1[s][j]);
-                }
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < SPT; ++s) {
-            uint32_t even[4], odd[4];
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                even[j] = pr[s][j].x;
-                odd[j] = pr[s][j].y;
-            }
-            float w[4][2];
-            lean_weights(c[s], w);
-            *reinterpret_cast<uint32_t*>(o8 + (min(i[s], N - 1u) << 2)) = lean_interp<BF>(w, even, odd);
-        }
-    }
 }
 
 // The same over RUNS of four consecutive samples per thread (see k_grid_fwd_runs): the first proposal level's samples are
@@ -1237,7 +920,8 @@ k_grid_fwd_small_runs(NvoGridLevels g, uint32_t N, const float* __restrict__ x, 
 
 // k_grid_fwd_runs, INSTRUCTION-LEAN (round 6): the run-walking inference form of the main grid's forward (plan and tile
 // shape of k_grid_fwd_runs: a thread walks four consecutive samples of ONE level, block-uniform) with the arithmetic of
-// k_grid_fwd_lean.  Bit-identical to k_grid_fwd.
+// k_grid_fwd_small_lean: the level's kind is block-uniform and takes one of two straight-line paths.  Bit-identical to
+// k_grid_fwd.
 template <int BLOCK, bool BF>
 __global__ void __launch_bounds__(BLOCK)
 k_grid_fwd_runs_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const __half2* __restrict__ table,
@@ -1653,7 +1337,7 @@ __device__ __forceinline__ void grid_bwd_item(const NvoGridLevels& g, uint32_t N
                                               const uint32_t* __restrict__ live = nullptr, bool merge = false,
                                               uint32_t slice_cap = ACC::kEntries, uint32_t* __restrict__ nf_flag = nullptr,
                                               const uint32_t* __restrict__ live_n = nullptr, uint32_t ring_off = 0u,
-                                              const uint16_t* __restrict__ codes = nullptr, uint32_t list_pass = 4096u) {
+                                              uint32_t list_pass = 4096u) {
     typename ACC::T* acc = reinterpret_cast<typename ACC::T*>(lds_raw);
     const uint32_t off = g.offset[level];
     const uint32_t size = g.offset[level + 1] - off;
@@ -1818,86 +1502,6 @@ __device__ __forceinline__ void grid_bwd_item(const NvoGridLevels& g, uint32_t N
             }
             if (open && hit) flush();
         }
-    } else if (pair_bins && ring_off != 0u && codes != nullptr && sizeof(DY2) == 4 && ACC::kEntries == 16384u) {
-      if constexpr (sizeof(DY2) == 4 && ACC::kEntries == 16384u) {  // (the launcher hands codes to this combination only)
-        // HASHED level, SLICE CODES (round 6).  The scan below this branch derives every sample's cell, two 32-bit
-        // multiplies and four hashes on EVERY one of the level's 8 slice visits to find the one (y, z) pair in eight that
-        // lands in the slice: ~100 vector instructions per sample and visit, and the launch is bound by exactly that
-        // (1 M samples x 16 hashed visits on ~250 CUs at one wave instruction per cycle and CU).  k_slice_codes derives them
-        // ONCE per (sample, level) and leaves 12 bits -- the slice of each of the four (y, z) pairs; a visit here is a
-        // 2-byte code + the 4-byte gradient, four field compares and one push of {sample | pair mask, gradient} for the
-        // ~40 % of the samples that touch the slice at all; the cell, the hashes and the weights are computed when 64
-        // entries are drained, with every lane busy.  Same products, integer accumulation: bit-identical gradients.
-        const uint32_t my = (first >> 14) & 7u;
-        constexpr uint32_t kCap = 2u * kHitCap;  // 8-byte entries in the wave's ring
-        uint2* const ring = reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(lds_raw) + ring_off) +
-                            (threadIdx.x >> 6) * kCap;
-        uint32_t q_head = 0u, q_fill = 0u;
-        auto q_drain = [&](uint32_t n) {  // the n <= 64 oldest entries
-            if (lane_id < n) {
-                uint32_t p = q_head + lane_id;
-                if (p >= kCap) p -= kCap;
-                const uint2 e = ring[p];
-                const uint32_t i = e.x & 0x0FFFFFFFu, m = e.x >> 28;
-                const float2 d = dy2f(__builtin_bit_cast(DY2, e.y));
-                const float* xp = x + 3 * (size_t)i;
-                const Corner c = grid_cell(scale, xp[0], xp[1], xp[2]);
-                const float wx0 = 1.f - c.wx, wy0 = 1.f - c.wy, wz0 = 1.f - c.wz;
-                const float wyz[4] = {wy0 * wz0, c.wy * wz0, wy0 * c.wz, c.wy * c.wz};
-                const uint32_t hy0 = c.py * 2654435761u, hy1 = hy0 + 2654435761u;
-                const uint32_t hz0 = c.pz * 805459861u, hz1 = hz0 + 805459861u;
-                const uint32_t a[4] = {hy0 ^ hz0, hy1 ^ hz0, hy0 ^ hz1, hy1 ^ hz1};
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    if ((m >> j) & 1u) {
-                        const uint32_t lo = a[j] & mask & (ACC::kEntries - 1u);
-                        const float u0 = wyz[j] * d.x, u1 = wyz[j] * d.y;
-                        ACC::add(acc, lo ^ c.px, wx0 * u0, wx0 * u1, sc);
-                        ACC::add(acc, lo ^ (c.px + 1u), c.wx * u0, c.wx * u1, sc);
-                    }
-                }
-            }
-            q_head += n;
-            if (q_head >= kCap) q_head -= kCap;
-            q_fill -= n;
-        };
-        for (uint32_t c0 = wave_grab(64u * kUnroll); begin + c0 < end; c0 = wave_grab(64u * kUnroll)) {
-            const uint32_t i0 = begin + c0 + lane_id;
-            uint32_t sid[kUnroll], code[kUnroll], dyr[kUnroll];
-#pragma unroll
-            for (uint32_t u = 0; u < kUnroll; ++u) {
-                const uint32_t j = i0 + u * 64u;
-                sid[u] = j < end ? (listed ? live[j] : j) : 0u;
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < kUnroll; ++u) {  // (unconditional loads at a valid index; slots past the end are masked below)
-                code[u] = codes[sid[u]];
-                const DY2 d2 = SOA ? dy[(size_t)level * N + sid[u]] : dy[(size_t)sid[u] * g.n_levels + level];
-                dyr[u] = __builtin_bit_cast(uint32_t, d2);
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < kUnroll; ++u) {
-                const bool valid = i0 + u * 64u < end;
-                const float2 d = dy2f(__builtin_bit_cast(DY2, dyr[u]));
-                bad = bad || (valid && (!(fabsf(d.x) < INFINITY) || !(fabsf(d.y) < INFINITY)));
-                uint32_t m = 0u;
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) m |= (((code[u] >> (3u * j)) & 7u) == my ? 1u : 0u) << j;
-                const bool hit = valid && m != 0u && (d.x != 0.f || d.y != 0.f);
-                // (wave-uniform control flow around the ballot, as in the scan below)
-                const unsigned long long bm = __ballot(hit);
-                const uint32_t cnt = (uint32_t)__popcll(bm);
-                if (hit) {
-                    uint32_t p = q_head + q_fill + __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
-                    if (p >= kCap) p -= kCap;
-                    ring[p] = make_uint2(sid[u] | (m << 28), dyr[u]);
-                }
-                q_fill += cnt;  // (< 64 before, <= 64 more: never beyond the ring's 254 entries)
-                if (q_fill >= 64u) q_drain(64u);
-            }
-        }
-        while (q_fill) q_drain(min(q_fill, 64u));
-      }
     } else if (pair_bins && ring_off != 0u) {
         // HASHED level with a hit queue (kHitCap).  Everything up to the slice test runs for all 64 lanes; the pairs that
         // fall into this slice (one in `slices of the level` on average) are pushed into the wave's ring -- 16 bytes:
@@ -2144,32 +1748,6 @@ k_dy_l1(NvoGridLevels g, uint32_t N, const DY2* __restrict__ dy, unsigned long l
     }
 }
 
-// Slice codes of the hashed levels in `levels` (bit l): codes[row][i] = the 16384-entry slice of each of sample i's four
-// (y, z) corner pairs on that level, 3 bits each (pair j in bits 3 j .. 3 j + 2); row = rank of the level among the coded
-// ones.  A level qualifies when it is hashed, a power-of-two multiple of 16384 entries with at most 8 slices, and every x
-// coordinate stays below the slice bits (the slice-owner items' `pair_bins` condition): the slice is then a function of
-// the (y, z) hash alone.  One pass over the positions; what the slice owners otherwise re-derive on every visit.
-__global__ void __launch_bounds__(256)
-k_slice_codes(NvoGridLevels g, uint32_t N, const float* __restrict__ x, uint32_t levels, uint16_t* __restrict__ codes) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= N) return;
-    const float px = x[3 * (size_t)i], py = x[3 * (size_t)i + 1], pz = x[3 * (size_t)i + 2];
-    uint32_t row = 0;
-    for (uint32_t l = 0; l < g.n_levels; ++l) {
-        if (!((levels >> l) & 1u)) continue;  // (uniform)
-        const uint32_t mask = g.offset[l + 1] - g.offset[l] - 1u;
-        const Corner c = grid_cell(g.scale[l], px, py, pz);
-        const uint32_t hy0 = c.py * 2654435761u, hy1 = hy0 + 2654435761u;
-        const uint32_t hz0 = c.pz * 805459861u, hz1 = hz0 + 805459861u;
-        const uint32_t a[4] = {hy0 ^ hz0, hy1 ^ hz0, hy0 ^ hz1, hy1 ^ hz1};
-        uint32_t code = 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) code |= (((a[j] & mask) >> 14) & 7u) << (3u * j);
-        codes[(size_t)row * N + i] = (uint16_t)code;
-        ++row;
-    }
-}
-
 template <bool SOA, typename DY2>
 __global__ void __launch_bounds__(kLdsBwdBlock)
 k_grid_bwd_lds(NvoGridLevels g, uint32_t N, const float* __restrict__ x,
@@ -2177,7 +1755,7 @@ k_grid_bwd_lds(NvoGridLevels g, uint32_t N, const float* __restrict__ x,
                const uint4* __restrict__ items, const unsigned long long* __restrict__ l1,
                const uint32_t* __restrict__ live, uint32_t* __restrict__ nf_flag, const uint32_t* __restrict__ live_n,
                uint32_t ring_off, const float* __restrict__ ext_l1, uint32_t ext_blocks, uint32_t ext_stride,
-               const uint16_t* __restrict__ codes, uint32_t code_levels, uint32_t list_pass) {
+               uint32_t list_pass) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const uint4 item = items[blockIdx.x];  // {level, first entry, chunk, n_chunks | accumulator-kind flags}
     const uint32_t n_chunks = item.w & 0x1FFFFFFFu;
@@ -2212,7 +1790,7 @@ k_grid_bwd_lds(NvoGridLevels g, uint32_t N, const float* __restrict__ x,
     }
     if (item.w >> 31) {
         grid_bwd_item<AccFloat, SOA, DY2>(g, N, x, dy, grad, level, item.y, item.z, n_chunks, lds_raw,
-                                          AccScale{0.f, 0.f, 0.f, 0.f}, live, merge, cap, nf_flag, live_n, 0u, nullptr, list_pass);
+                                          AccScale{0.f, 0.f, 0.f, 0.f}, live, merge, cap, nf_flag, live_n, 0u, list_pass);
     } else if ((item.w >> 30) & 1u) {
         const float l1x = ext_l1 ? l1e[0] : (float)l1[2 * level] * (1.f / 256.f);
         const float l1y = ext_l1 ? l1e[1] : (float)l1[2 * level + 1] * (1.f / 256.f);
@@ -2221,14 +1799,11 @@ k_grid_bwd_lds(NvoGridLevels g, uint32_t N, const float* __restrict__ x,
         sc.s1 = l1y > 0.f ? 536870912.f / l1y : 0.f;
         sc.inv0 = l1x * (1.f / 536870912.f);
         sc.inv1 = l1y * (1.f / 536870912.f);
-        // (slice codes of this level, k_slice_codes: row = number of coded levels below it)
-        const uint16_t* lc = (codes && ((code_levels >> level) & 1u))
-                                 ? codes + (size_t)__builtin_popcount(code_levels & ((1u << level) - 1u)) * N : nullptr;
         grid_bwd_item<AccFixed32, SOA, DY2>(g, N, x, dy, grad, level, item.y, item.z, n_chunks, lds_raw, sc, live,
-                                            merge, cap, nf_flag, live_n, ring_off, lc, list_pass);
+                                            merge, cap, nf_flag, live_n, ring_off, list_pass);
     } else {
         grid_bwd_item<AccFixed, SOA, DY2>(g, N, x, dy, grad, level, item.y, item.z, n_chunks, lds_raw,
-                                          AccScale{0.f, 0.f, 0.f, 0.f}, live, merge, cap, nf_flag, live_n, 0u, nullptr, list_pass);
+                                          AccScale{0.f, 0.f, 0.f, 0.f}, live, merge, cap, nf_flag, live_n, 0u, list_pass);
     }
 }
 
@@ -2463,28 +2038,28 @@ __device__ __forceinline__ TlItem tl_decode(uint4 h, uint32_t n_tiles) {
 // The tile writes L1_f(tile, bin) <= S_f * M_f / 1023, rounded UP to bf16, next to its segment word; the accumulate item
 // sums the words of its tiles (fixed order) and scales by 2^29 / L1.  Everything that feeds the scale is integer or
 // fixed-order arithmetic, so single-chunk bins stay bitwise reproducible.
-constexpr uint32_t kBinP = 8192;   // largest bin of the packed form (13-bit entry index in a record)
-constexpr uint32_t kBinPSmall = 6176;  // (experiment, NVO_TL_BIN=6176: 85 bins per 2^19 table; measured slower)
+// entries per bin: 8192 x 8 B = 64 KiB, the largest bin of the packed form (13-bit entry index in a record).  (6176-entry
+// bins -- 85 per 2^19 table, 935 hashed items = two even rounds of 512 workgroups on paper -- measured SLOWER: 139.0 /
+// 146.1 us for the stage against 132.8 / 127.3 with 8192-entry bins: the shorter runs cost more than the evener rounds save.)
+constexpr uint32_t kBinP = 8192;
 constexpr int kTlBlockP = 512;
 // wave loads of pair records per pass (a hashed item's 48 runs x ~32 pairs per wave = 24 loads).  14 is what 128 VGPRs
 // hold (5 per window); 24 in one pass needs 175 and halves the occupancy (81 us), 256-thread workgroups with 32 windows
 // measured 69.7 us against 52.2
 constexpr uint32_t kTlWinP = 14;
 
-template <uint32_t BIN>
 __device__ __forceinline__ uint32_t st_bin_entries_p(const NvoGridLevels& g, uint32_t level, uint32_t slice) {
     const uint32_t size = g.offset[level + 1] - g.offset[level];
-    return min(BIN, size - slice * BIN);
+    return min(kBinP, size - slice * kBinP);
 }
 
-template <uint32_t BIN>
 __global__ void __launch_bounds__(256)
 k_st_zero_p(NvoGridLevels g, const uint32_t* __restrict__ bin_level, const uint32_t* __restrict__ bin_slice,
             const uint32_t* __restrict__ bin_chunks, float* __restrict__ grad) {
     if (bin_chunks[blockIdx.x] <= 1u) return;
     const uint32_t level = bin_level[blockIdx.x], slice = bin_slice[blockIdx.x];
-    const uint32_t n = 2 * st_bin_entries_p<BIN>(g, level, slice);
-    float* __restrict__ gr = grad + 2 * ((size_t)g.offset[level] + (size_t)slice * BIN);
+    const uint32_t n = 2 * st_bin_entries_p(g, level, slice);
+    float* __restrict__ gr = grad + 2 * ((size_t)g.offset[level] + (size_t)slice * kBinP);
     for (uint32_t e = threadIdx.x; e < n; e += 256) gr[e] = 0.f;
 }
 
@@ -2523,7 +2098,7 @@ __device__ __forceinline__ PairRec pair_pack(uint32_t rel, float u0, float u1, u
     return PairRec{(a & ~0x3Fu) | (rel & 0x3Fu), (b & ~0x7Fu) | (rel >> 6), (wq & 0xFFFFu) | (code << 16)};
 }
 
-template <int TILE, bool SOA, typename DY2, uint32_t BIN, bool LISTED>
+template <int TILE, bool SOA, typename DY2, bool LISTED>
 __global__ void __launch_bounds__(TILE)
 k_tl_scatter_p(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const DY2* __restrict__ dy,
                const uint32_t* __restrict__ st_levels, const uint32_t* __restrict__ bin_first,
@@ -2607,7 +2182,7 @@ k_tl_scatter_p(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const D
             const uint32_t i1 = nvo_grid_index(hashed, size, res, c.px + 1u, cy, cz);
             const float wyz = ((j & 1u) ? c.wy : 1.f - c.wy) * ((j & 2u) ? c.wz : 1.f - c.wz);
             const float u0 = wyz * d.x, u1 = wyz * d.y;
-            const uint32_t b0 = i0 / BIN, b1 = i1 / BIN, r0 = i0 % BIN, r1 = i1 % BIN;
+            const uint32_t b0 = i0 / kBinP, b1 = i1 / kBinP, r0 = i0 % kBinP, r1 = i1 % kBinP;
             bin_a[j] = b0;
             bin_b[j] = b1;
             // second corner's offset from the first: xor with a low mask (hashed levels) or + 1 (dense levels)
@@ -2693,7 +2268,7 @@ k_tl_scatter_p(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const D
 // wrote nothing -- their words are stale and count as empty.  A separate instantiation: the pass runs at its scalar-register
 // limit (24 v_writelane in the plain form), and the three values the bound needs, kept through the item loop, tripled
 // the spills and cost every launch 12 us (86 -> 99 us alone) -- whether a list was in use or not.
-template <uint32_t BIN, bool LISTED>
+template <bool LISTED>
 __global__ void __launch_bounds__(kTlBlockP, 4)
 k_tl_accumulate_p(NvoGridLevels g, const uint4* __restrict__ items, uint32_t n_items, const uint32_t* __restrict__ seg,
                   const uint32_t* __restrict__ segl1, const uint32_t* __restrict__ records, uint32_t n_tiles,
@@ -2756,8 +2331,8 @@ k_tl_accumulate_p(NvoGridLevels g, const uint4* __restrict__ items, uint32_t n_i
             segw = cur.n_chunks ? words_first(cur, &l1w) : 0u;
             continue;
         }
-        const uint32_t entries = st_bin_entries_p<BIN>(g, cur.level, cur.slice);
-        float* __restrict__ gr = grad + 2 * ((size_t)g.offset[cur.level] + (size_t)cur.slice * BIN);
+        const uint32_t entries = st_bin_entries_p(g, cur.level, cur.slice);
+        float* __restrict__ gr = grad + 2 * ((size_t)g.offset[cur.level] + (size_t)cur.slice * kBinP);
         GP_CLK(gp0);
         {
             uint4* z = reinterpret_cast<uint4*>(lds_raw);  // one uint4 = two entries
@@ -2874,7 +2449,7 @@ k_tl_accumulate_p(NvoGridLevels g, const uint4* __restrict__ items, uint32_t n_i
                 // the bin's gradient is complete right here: step its entries instead of storing it (skipped step: the
                 // gradient is not needed either)
                 if (!adam_skip) {
-                    const size_t o4 = ((size_t)g.offset[cur.level] + (size_t)cur.slice * BIN) >> 1;  // in float4 units
+                    const size_t o4 = ((size_t)g.offset[cur.level] + (size_t)cur.slice * kBinP) >> 1;  // in float4 units
                     float4* __restrict__ p4 = reinterpret_cast<float4*>(adam.params) + o4;
                     float4* __restrict__ m4 = reinterpret_cast<float4*>(adam.exp_avg) + o4;
                     float4* __restrict__ v4 = reinterpret_cast<float4*>(adam.exp_avg_sq) + o4;
@@ -3076,7 +2651,7 @@ k_sum_levels(uint32_t n_levels, size_t n, const float* __restrict__ partial, flo
 // Builds the XCD-balanced plan (see GridFwdPlan); returns the blocks per XCD (grid = 8 x that), plan->enabled = 0 when
 // the level set does not fit the scheme (fewer than 8 hashed levels, too many pieces).
 static uint32_t grid_fwd_plan_build(const NvoGridLevels& g, uint32_t tiles, GridFwdPlan* plan) {
-    static const float dense_cost = [] { const char* e = getenv("NVO_GRID_FWD_DENSE_COST"); return e ? (float)atof(e) : 0.4f; }();
+    constexpr float dense_cost = 0.4f;  // a dense level's tile relative to a hashed level's (neighbouring corners, L2 hits)
     std::vector<uint32_t> hashed, dense;
     for (uint32_t l = 0; l < g.n_levels; ++l) (g.hashed[l] ? hashed : dense).push_back(l);
     if (hashed.size() < 8 || hashed.size() > 16) return 0;
@@ -3157,10 +2732,13 @@ int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, 
                 g.n_features);
     NVO_PROF(stream, "grid_fwd[L%u]", g.n_levels);
     // small grids (the proposal networks): the two coarsest dense levels from LDS, a thread per sample (k_grid_fwd_small)
-    // 0 off | 1 plain | 2 two samples per thread (measured slower: 35.0 vs 33.6 us) | 3 software-pipelined (round 6: no gain,
-    // the kernel is bound by vector-instruction issue) | 4 instruction-lean + pipelined (round 6, default)
-    static const int small_default = [] { const char* e = getenv("NVO_GRID_FWD_SMALL"); return e ? atoi(e) : 4; }();
-    const int small_env = small_form >= 0 ? small_form : small_default;  // (module option grid_fwd_small_form: tests, A/B)
+    // 0 off | 1 plain | 4 instruction-lean + pipelined (round 6, default: 33.8 -> 23.5 us per 1 M-sample launch).  (Forms 2,
+    // two samples per thread: 35.0 vs 33.6 us, and 3, software-pipelined alone: 35.6 vs 33.8 us, are gone -- EXPERIMENTS.md
+    // 10.3, 12.1.)
+    constexpr int kSmallFormDefault = 4;
+    NVO_REQUIRE(small_form == -1 || small_form == 0 || small_form == 1 || small_form == 4,
+                "grid: small-grid forward form %d (-1 default, 0 generic, 1 plain, 4 instruction-lean)", small_form);
+    const int small_env = small_form >= 0 ? small_form : kSmallFormDefault;  // (module option grid_fwd_small_form: tests, A/B)
     if (small_env && soa && !indices && !dydx_half && !n_live && g.n_levels == 5 && !g.hashed[0] && !g.hashed[1] &&
         (size_t)g.offset[2] * 4 <= 152 * 1024 && (g.offset[2] & 3u) == 0u && (((uintptr_t)table_half) & 15u) == 0u) {
         static const uint32_t n_cus = [] {
@@ -3171,11 +2749,7 @@ int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, 
         const size_t lds = (size_t)g.offset[2] * 4;
         static bool attr_set = false;
         if (!attr_set) {
-            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_grid_fwd_small<2, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              152 * 1024));
-            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_grid_fwd_small<2, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              152 * 1024));
-            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_grid_fwd_small_pipe<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize,
+            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_grid_fwd_small<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                               152 * 1024));
             attr_set = true;
         }
@@ -3214,8 +2788,6 @@ int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, 
             NVO_CHECK_LAUNCH();
             return NVO_OK;
         }
-        // one workgroup per CU, a whole number of passes each
-        const uint32_t spt = small_env == 2 ? 2u : 1u;
         const uint32_t hmask = (g.hashed[2] ? 1u : 0u) | (g.hashed[3] ? 2u : 0u) | (g.hashed[4] ? 4u : 0u);
         if (small_env >= 4 && (hmask == 6u || hmask == 7u || hmask == 4u) && (uint64_t)N * 20u < (1ull << 32) &&
             g.resolution[0] <= 4096u && g.resolution[1] <= 4096u && g.resolution[2] <= 4096u) {
@@ -3240,79 +2812,51 @@ int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, 
             NVO_CHECK_LAUNCH();
             return NVO_OK;
         }
-        const uint32_t per_block = (uint32_t)nvo_round_up(nvo_div_up(N, n_cus), kSmallBlock * spt);
-        if (small_env >= 3)
-            NVO_LAUNCH((k_grid_fwd_small_pipe<2, 3>), dim3(nvo_div_up(N, per_block)), dim3(kSmallBlock), lds, stream, g, N, x,
-                       (const __half2*)table_half, (__half2*)out_half, out_bf16 ? 1 : 0, per_block);
-        else if (spt == 2)
-            NVO_LAUNCH((k_grid_fwd_small<2, 3, 2>), dim3(nvo_div_up(N, per_block)), dim3(kSmallBlock), lds, stream, g, N, x,
-                       (const __half2*)table_half, (__half2*)out_half, out_bf16 ? 1 : 0, per_block);
-        else
-            NVO_LAUNCH((k_grid_fwd_small<2, 3, 1>), dim3(nvo_div_up(N, per_block)), dim3(kSmallBlock), lds, stream, g, N, x,
-                       (const __half2*)table_half, (__half2*)out_half, out_bf16 ? 1 : 0, per_block);
+        // the plain form (and the shapes the lean form refuses): one workgroup per CU, a whole number of passes each
+        const uint32_t per_block = (uint32_t)nvo_round_up(nvo_div_up(N, n_cus), kSmallBlock);
+        NVO_LAUNCH((k_grid_fwd_small<2, 3>), dim3(nvo_div_up(N, per_block)), dim3(kSmallBlock), lds, stream, g, N, x,
+                   (const __half2*)table_half, (__half2*)out_half, out_bf16 ? 1 : 0, per_block);
         NVO_CHECK_LAUNCH();
         return NVO_OK;
     }
-    static const int spt_env = [] { const char* e = getenv("NVO_GRID_FWD_SPT"); return e ? atoi(e) : 2; }();
     // option "grid_fwd_runs": four consecutive samples per thread (k_grid_fwd_runs) wherever its 16-byte accesses line up
     runs = runs && soa && !indices && !dydx_half && (N & 3u) == 0u && (((uintptr_t)x) & 15u) == 0u &&
            (((uintptr_t)out_half) & 15u) == 0u;
-    const int spt = runs ? 4 : (dydx_half || spt_env < 2) ? 1 : (spt_env >= 4 ? 4 : 2);  // samples per thread
+    // samples per thread of k_grid_fwd: two (the gathers of both in flight, see there), one with the dydx output
+    constexpr int kFwdSpt = 2;
+    const int spt = runs ? 4 : dydx_half ? 1 : kFwdSpt;
     const uint32_t tiles = nvo_div_up(N, kGridBlock * spt);
     dim3 grid(tiles * g.n_levels), block(kGridBlock);
     GridFwdPlan plan;
     memset(&plan, 0, sizeof(plan));
-    static const int balance_env = [] { const char* e = getenv("NVO_GRID_FWD_BALANCE"); return e ? atoi(e) : 1; }();
-    if (balance_env && (g.n_levels & 7u) == 0u) {
+    if ((g.n_levels & 7u) == 0u) {
         const uint32_t blocks_per_xcd = grid_fwd_plan_build(g, tiles, &plan);
         if (plan.enabled) grid = dim3(8u * blocks_per_xcd);
     }
 #define NVO_LAUNCH_FWD_S(SOA_, DYDX_, SPT_)                                                                  \
     NVO_LAUNCH((k_grid_fwd<SOA_, DYDX_, SPT_>), grid, block, 0, stream, g, N, x, (const __half2*)table_half, \
                (__half2*)out_half, indices, (__half2*)dydx_half, out_bf16 ? 1 : 0, plan, n_live)
-#define NVO_LAUNCH_FWD(SOA_, DYDX_)                                        \
+#define NVO_LAUNCH_FWD(SOA_)                                               \
     do {                                                                   \
-        if (DYDX_ || spt == 1) NVO_LAUNCH_FWD_S(SOA_, DYDX_, 1);           \
-        else if (spt == 2) NVO_LAUNCH_FWD_S(SOA_, false, 2);               \
-        else NVO_LAUNCH_FWD_S(SOA_, false, 4);                             \
+        if (dydx_half) NVO_LAUNCH_FWD_S(SOA_, true, 1);                    \
+        else NVO_LAUNCH_FWD_S(SOA_, false, kFwdSpt);                       \
     } while (0)
-    // the instruction-lean form of the level-major production path (form 0 = the first kernel, kept as the reference form)
-    // NVO_GRID_FWD_LEAN=1 (A/B; default off): k_grid_fwd_lean for the main grid.  Measured (EXPERIMENTS 10.3): faster on
-    // samples clustered within 2 % of the surface (35.5 -> 30.9 us per training batch, 243 -> 199 us per render chunk) but
-    // SLOWER where the gather binds -- the spread samples of an untrained field: 59.5 -> 66 us -- and neutral inside the
-    // mapping loop (windows at iterations 5000 / 7900: 0.398 / 0.385 vs 0.395 / 0.385 ms); the first kernel stays.
-    static const bool lean_env = [] { const char* e = getenv("NVO_GRID_FWD_LEAN"); return e && atoi(e) != 0; }();
-    bool lean = lean_env && small_env != 0 && !runs && soa && !indices && !dydx_half && (uint64_t)N * 12u < (1ull << 32);
-    for (uint32_t l = 0; l < g.n_levels; ++l) lean = lean && g.resolution[l] <= 4096u;
-    // the run-walking inference form has a lean counterpart as well (form 0 = the first kernel)
-    static const bool lean_runs_env = [] { const char* e = getenv("NVO_GRID_FWD_RUNS_LEAN"); return !e || atoi(e) != 0; }();  // A/B
-    bool lean_runs = lean_runs_env && small_env != 0 && runs && (uint64_t)N * 12u < (1ull << 32);
+    // The main grid's training forward stays the first kernel: an instruction-lean form of it (as k_grid_fwd_small_lean)
+    // was faster on samples clustered at the surface but SLOWER where the gather binds -- the spread samples of an
+    // untrained field: 59.5 -> 66 us -- and neutral inside the mapping loop (EXPERIMENTS.md 10.4; removed in 12.1).
+    // The run-walking inference form does have a lean counterpart (form 0 = the first kernel).
+    bool lean_runs = small_env != 0 && runs && (uint64_t)N * 12u < (1ull << 32);
     for (uint32_t l = 0; l < g.n_levels; ++l) lean_runs = lean_runs && g.resolution[l] <= 4096u;
-    if (lean) {
-        static const bool pair_env = [] { const char* e = getenv("NVO_GRID_FWD_PAIR"); return !e || atoi(e) != 0; }();  // A/B (default on)
-#define NVO_LAUNCH_LEANM(SPT_, BF_, PAIR_)                                                                   \
-    NVO_LAUNCH((k_grid_fwd_lean<SPT_, BF_, PAIR_>), grid, block, 0, stream, g, N, x, (const __half2*)table_half, \
-               (__half2*)out_half, plan, n_live)
-#define NVO_LAUNCH_LEANS(SPT_)                                                                               \
-    do {                                                                                                     \
-        if (pair_env) { if (out_bf16) NVO_LAUNCH_LEANM(SPT_, true, true); else NVO_LAUNCH_LEANM(SPT_, false, true); } \
-        else { if (out_bf16) NVO_LAUNCH_LEANM(SPT_, true, false); else NVO_LAUNCH_LEANM(SPT_, false, false); } \
-    } while (0)
-        if (spt == 1) NVO_LAUNCH_LEANS(1);
-        else if (spt == 2) NVO_LAUNCH_LEANS(2);
-        else NVO_LAUNCH_LEANS(4);
-#undef NVO_LAUNCH_LEANS
-#undef NVO_LAUNCH_LEANM
-    } else if (runs && lean_runs) {
+    if (lean_runs) {
         if (out_bf16) NVO_LAUNCH((k_grid_fwd_runs_lean<kGridBlock, true>), grid, block, 0, stream, g, N, x, (const __half2*)table_half, (__half2*)out_half, plan, n_live);
         else NVO_LAUNCH((k_grid_fwd_runs_lean<kGridBlock, false>), grid, block, 0, stream, g, N, x, (const __half2*)table_half, (__half2*)out_half, plan, n_live);
     } else if (runs) {
         NVO_LAUNCH((k_grid_fwd_runs<kGridBlock>), grid, block, 0, stream, g, N, x, (const __half2*)table_half,
                    (__half2*)out_half, out_bf16 ? 1 : 0, plan, n_live);
     } else if (soa) {
-        if (dydx_half) NVO_LAUNCH_FWD(true, true); else NVO_LAUNCH_FWD(true, false);
+        NVO_LAUNCH_FWD(true);
     } else {
-        if (dydx_half) NVO_LAUNCH_FWD(false, true); else NVO_LAUNCH_FWD(false, false);
+        NVO_LAUNCH_FWD(false);
     }
 #undef NVO_LAUNCH_FWD
 #undef NVO_LAUNCH_FWD_S
@@ -3322,19 +2866,15 @@ int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, 
 
 // Slice tables for the LDS backward live in a small device buffer owned by the module.
 
-int nvo_grid_slices_create(const NvoGridLevels& g, NvoGridSlices* s, uint32_t level_mask, uint32_t target,
-                           bool env_items) {
+int nvo_grid_slices_create(const NvoGridLevels& g, NvoGridSlices* s, uint32_t level_mask, uint32_t target) {
     static_assert(2 * AccFixed32::kEntries * sizeof(int) <= kLdsBwdBytes, "32-bit slice does not fit the LDS");
     struct Item { uint32_t level, first, chunk, n_chunks; };
     // Per level: accumulator kind and slice size.  Large hashed tables (>= 2^18 entries: a 20K-entry
     // slice sees <= 8 % of the lookups) use fp32 / 20K-entry slices, everything else 64-bit fixed
-    // point / 8K-entry slices.  NVO_GRID_BWD_ACC = "fixed" | "float" forces one kind (experiments).
-    const char* force = getenv("NVO_GRID_BWD_ACC");
+    // point / 8K-entry slices.
     const bool acc32 = s->acc_bits == 32;  // 32-bit fixed point with the L1-derived scale, every level
     auto float_mode = [&](uint32_t l) {
         if (acc32 || s->deterministic) return false;  // (LDS float atomics retire in no fixed order)
-        if (force && !strcmp(force, "fixed")) return false;
-        if (force && !strcmp(force, "float")) return true;
         return g.hashed[l] && (g.offset[l + 1] - g.offset[l]) >= (1u << 18);
     };
     // entries per slice of a level; fixed_cap (< 8192, dense levels only) shrinks the 64-bit fixed-point slices so that
@@ -3347,14 +2887,12 @@ int nvo_grid_slices_create(const NvoGridLevels& g, NvoGridSlices* s, uint32_t le
     // pass 1: chunk counts from the hit share alone (unit = share of one float slice of a 2^19
     // table); pass 2: scale them so that the launch has enough (>= target) items to fill 256 CUs
     // for several rounds.
-    if (const char* env = env_items ? getenv("NVO_GRID_BWD_ITEMS") : nullptr) target = (uint32_t)atoi(env);
     s->level_mask = level_mask;
     auto base_chunks = [&](uint32_t count, uint32_t size) {
         const double share = (double)count / (double)size * (524288.0 / (double)kSliceFloat);
         uint32_t n = (uint32_t)(share + 0.5);
         return n < 1 ? 1u : n;
     };
-    if (const char* e = getenv("NVO_GRID_RUNS")) s->runs = atoi(e) != 0;  // A/B switch for measurements
     uint32_t base_total = 0;
     for (uint32_t l = 0; l < g.n_levels; ++l) {
         if (!((level_mask >> l) & 1u)) continue;
@@ -3376,7 +2914,6 @@ int nvo_grid_slices_create(const NvoGridLevels& g, NvoGridSlices* s, uint32_t le
         }
         int dev = 0, n_cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (const char* e = getenv("NVO_GRID_ROUND_CUS")) n_cus = atoi(e);  // measurements
         if (n_total && n_total <= (uint32_t)n_cus) {
             const uint64_t pass = (uint64_t)kLdsBwdBlock * 8;
             const uint32_t per = (uint32_t)n_cus / n_total;
@@ -3398,14 +2935,6 @@ int nvo_grid_slices_create(const NvoGridLevels& g, NvoGridSlices* s, uint32_t le
                     hashed_chunks = ch;
                 }
             }
-        }
-    }
-    if (const char* e = getenv("NVO_GRID_CHUNKS")) {  // measurements: "dense,hashed" chunks per slice
-        unsigned d = 0, h = 0;
-        if (sscanf(e, "%u,%u", &d, &h) == 2 && d && h) {
-            even_chunks = d;
-            dense_chunks = d;
-            hashed_chunks = h;
         }
     }
     // Most expensive first: single-chunk items scan all N samples (long), chunked items scan
@@ -3459,7 +2988,6 @@ int nvo_grid_slices_create(const NvoGridLevels& g, NvoGridSlices* s, uint32_t le
 
 void nvo_grid_slices_destroy(NvoGridSlices* s) {
     nvo_scratch_destroy(&s->live);
-    nvo_scratch_destroy(&s->codes);
     if (s->d_level) (void)hipFree(s->d_level);
     s->d_level = s->d_first = nullptr;
     s->d_l1 = nullptr;
@@ -3493,21 +3021,11 @@ int nvo_grid_stream_create(const NvoGridLevels& g, NvoGridStream* st) {
     std::vector<uint32_t> levels, first, bin_level, bin_slice;
     st->max_slices = 0;
     st->streamed_mask = 0;
-    if (const char* e = getenv("NVO_GRID_STREAM_OVERLAP")) st->overlap = atoi(e) != 0;  // A/B switch for measurements
-    if (const char* e = getenv("NVO_GRID_OWNER_SLICES")) st->owner_max_slices = (uint32_t)atoi(e);  // measurements
-    // entries per bin: 8192 x 8 B (two 32-bit fixed-point sums in one 64-bit word) = 64 KiB
-    // (6176-entry bins -- 85 per 2^19 table, 935 hashed items = two even rounds of 512 workgroups on paper -- measured
-    // SLOWER: 139.0 / 146.1 us for the stage against 132.8 / 127.3 with 8192-entry bins (dealt / balanced work list):
-    // the shorter runs cost more than the evener rounds save)
-    uint32_t bin_p = kBinP;
-    if (const char* e = getenv("NVO_TL_BIN")) bin_p = (uint32_t)atoi(e) == kBinPSmall ? kBinPSmall : kBinP;  // measurements
-    const uint32_t bin_entries = bin_p;
-    st->bin_entries = bin_entries;
     for (uint32_t l = 0; l < g.n_levels; ++l) {
         const uint32_t size = g.offset[l + 1] - g.offset[l];
         // (which levels stay slice-owner is decided in 4096-entry units, whatever the bin size)
         if ((size + kBinSlice - 1u) / kBinSlice <= st->owner_max_slices) continue;
-        const uint32_t n_slices = (size + bin_entries - 1u) / bin_entries;
+        const uint32_t n_slices = (size + kBinP - 1u) / kBinP;
         levels.push_back(l);
         first.push_back((uint32_t)bin_level.size());
         if (n_slices > st->max_slices) st->max_slices = n_slices;
@@ -3538,8 +3056,6 @@ int nvo_grid_stream_create(const NvoGridLevels& g, NvoGridStream* st) {
         // static work list: hashed levels spread their records evenly over the bins (one item per bin); a streamed
         // DENSE level sees clustered samples, so its bins are split into tile ranges
         std::vector<uint32_t> items, chunks(nb, 1u);
-        const bool spread = !(getenv("NVO_TL_ORDER") && atoi(getenv("NVO_TL_ORDER")) == 0);
-        if (const char* e = getenv("NVO_TL_DENSE_CHUNKS")) st->dense_chunks = (uint32_t)atoi(e);
         if (st->deterministic) st->dense_chunks = 1;  // the tile ranges of a bin meet in float atomics: one item per bin
         for (uint32_t j = 0; j < levels.size(); ++j) {
             const uint32_t nc = g.hashed[levels[j]] ? 1u : st->dense_chunks;
@@ -3550,7 +3066,7 @@ int nvo_grid_stream_create(const NvoGridLevels& g, NvoGridStream* st) {
                 // workgroups of an XCD on the same few L2 channels: deal the bins so that an XCD gets CONSECUTIVE
                 // bins (8 x 8 transpose of the order inside each group of 64).
                 uint32_t bq = q;
-                if (spread && nbj >= 64 && q < (nbj & ~63u)) bq = (q & ~63u) | ((q & 7u) << 3) | ((q >> 3) & 7u);
+                if (nbj >= 64 && q < (nbj & ~63u)) bq = (q & ~63u) | ((q & 7u) << 3) | ((q >> 3) & 7u);
                 const uint32_t b = first[j] + bq;
                 chunks[b] = nc;
                 for (uint32_t c = 0; c < nc; ++c) {  // self-contained header (k_tl_accumulate: tl_decode)
@@ -3561,8 +3077,7 @@ int nvo_grid_stream_create(const NvoGridLevels& g, NvoGridStream* st) {
                 }
             }
         }
-        st->n_tl_slots = 0;
-        if (!(getenv("NVO_TL_BALANCE") && atoi(getenv("NVO_TL_BALANCE")) == 0)) {
+        {
             // BALANCED work list for the persistent accumulate (2 workgroups per CU, workgroup w walks items w, w + slots,
             // ...).  Dealt round-robin, 704 hashed-level items + 208 cheap dense-level chunks gave some workgroups two
             // hashed items and a chunk, others one hashed item: the launch lasted as long as the former (132.8 -> 127.3
@@ -3618,13 +3133,10 @@ int nvo_grid_stream_create(const NvoGridLevels& g, NvoGridStream* st) {
     // (a two-stage store + reduce form of the flush was measured slower)
     // measured optima for the coarse-only launch: 512 items (the atomic flush of a chunk costs as much as scanning ~2K
     // samples), 256 with the run-merging scan (cheaper scan, same flush)
+    constexpr uint32_t kOwnerItems = 512, kOwnerItemsRuns = 256;
     // 8000-entry slices: 125 KiB of LDS, which leaves room for a 512-sample scatter workgroup (32.5 KiB) on the same CU
     st->owner.fixed_cap = st->overlap ? 8000u : 0u;
-    if (const char* e = getenv("NVO_GRID_OWNER_CAP")) st->owner.fixed_cap = (uint32_t)atoi(e);  // measurements
-    if (const char* e = getenv("NVO_STREAM_OWNER_ACC_BITS")) st->owner.acc_bits = (uint32_t)atoi(e);  // measurements
-    uint32_t owner_items = st->owner.runs ? 256 : 512;
-    if (const char* e = getenv("NVO_GRID_OWNER_ITEMS")) owner_items = (uint32_t)atoi(e);  // measurements
-    return nvo_grid_slices_create(g, &st->owner, all & ~st->streamed_mask, owner_items, false);
+    return nvo_grid_slices_create(g, &st->owner, all & ~st->streamed_mask, st->owner.runs ? kOwnerItemsRuns : kOwnerItems);
 }
 
 void nvo_grid_stream_destroy(NvoGridStream* st) {
@@ -3672,11 +3184,6 @@ int nvo_grid_bwd_stream_launch(const NvoGridLevels& g, NvoGridStream* st, hipStr
     NVO_REQUIRE((uint64_t)N * 8 * g.n_levels < 0xFFFFFFFFull, "grid_bwd_stream: too many records for 32-bit offsets");
     if (N == 0) return nvo_zero_async(grad, sizeof(float) * 2 * (size_t)g.offset[g.n_levels], stream);
     NVO_PROF(stream, "grid_bwd_stream[L%u]", g.n_levels);
-    static const uint32_t n_cus = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return (uint32_t)(n > 0 ? n : 256);
-    }();
     const uint32_t tile = st->tile;
     const uint32_t n_tiles = nvo_div_up(N, tile);
     // fork: with the per-kernel profiler on, everything stays on the caller's stream (its events live there)
@@ -3733,50 +3240,49 @@ int nvo_grid_bwd_stream_launch(const NvoGridLevels& g, NvoGridStream* st, hipStr
     NVO_REQUIRE(tile == 512 || tile == 1024, "grid_bwd_stream: the packed accumulators take 512- or 1024-sample tiles");
     uint32_t* segl1 = reinterpret_cast<uint32_t*>(d_work + rec_bytes_tl + seg_bytes);
     const size_t lds_p = tile_records * 12 + (sizeof(unsigned long long) + sizeof(uint32_t)) * st->max_slices;
-    const size_t lds_acc_p = sizeof(unsigned long long) * st->bin_entries;
-    const uint32_t acc_grid = st->n_tl_slots ? st->n_tl_slots : (st->n_tl_items < 2 * n_cus ? st->n_tl_items : 2 * n_cus);
-#define NVO_LAUNCH_TLP_L(SOA_, T_, BIN_, TILE_, LISTED_)                                                      \
+    const size_t lds_acc_p = sizeof(unsigned long long) * kBinP;
+    const uint32_t acc_grid = st->n_tl_slots;  // (the persistent workgroups the balanced work list was laid out for)
+#define NVO_LAUNCH_TLP_L(SOA_, T_, TILE_, LISTED_)                                                            \
     do {                                                                                                      \
         static bool attr_set = false;                                                                         \
         if (!attr_set) {                                                                                      \
-            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_tl_scatter_p<TILE_, SOA_, T_, BIN_, LISTED_>,    \
+            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_tl_scatter_p<TILE_, SOA_, T_, LISTED_>,          \
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)(TILE_ * 96 + 12 * 4096))); \
-            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_tl_accumulate_p<BIN_, LISTED_>,                  \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(8 * BIN_)));  \
+            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_tl_accumulate_p<LISTED_>,                        \
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(8 * kBinP))); \
             attr_set = true;                                                                                  \
         }                                                                                                     \
         {                                                                                                     \
             NVO_PROF_SUB(stream, "tl_scatter[L%u]", g.n_levels);                                              \
-            NVO_LAUNCH((k_tl_scatter_p<TILE_, SOA_, T_, BIN_, LISTED_>), grid_tl, dim3(TILE_), lds_p, stream, g, N, x, (const T_*)dy, \
+            NVO_LAUNCH((k_tl_scatter_p<TILE_, SOA_, T_, LISTED_>), grid_tl, dim3(TILE_), lds_p, stream, g, N, x, (const T_*)dy, \
                        st->d_levels, st->d_bin_first, seg, segl1, reinterpret_cast<uint32_t*>(records_tl),     \
                        st->owner.nf_flag, live_list, live_n);                                                 \
         }                                                                                                     \
         {                                                                                                     \
             NVO_PROF_SUB(stream, "tl_accumulate[L%u]", g.n_levels);                                           \
             if (!st->external_zero)                                                                           \
-                NVO_LAUNCH(k_st_zero_p<BIN_>, dim3(st->n_bins), dim3(256), 0, stream, g, st->d_bin_level, st->d_bin_slice, \
+                NVO_LAUNCH(k_st_zero_p, dim3(st->n_bins), dim3(256), 0, stream, g, st->d_bin_level, st->d_bin_slice, \
                            st->d_bin_chunks, grad);                                                           \
-            NVO_LAUNCH((k_tl_accumulate_p<BIN_, LISTED_>), dim3(acc_grid), dim3(kTlBlockP), lds_acc_p, stream, g, \
+            NVO_LAUNCH((k_tl_accumulate_p<LISTED_>), dim3(acc_grid), dim3(kTlBlockP), lds_acc_p, stream, g, \
                        (const uint4*)st->d_tl_items, st->n_tl_items, seg, segl1,                              \
                        reinterpret_cast<const uint32_t*>(records_tl), n_tiles,                                \
                        (uint32_t)tile_records, grad, st->owner.nf_flag, st->adam, live_n, N);                 \
         }                                                                                                     \
     } while (0)
 /* (the listed forms are separate instantiations: see k_tl_accumulate_p) */                                   
-#define NVO_LAUNCH_TLP_B(SOA_, T_, BIN_, TILE_)                                                               \
-    do {                                                                                                      \
-        if (live_list) NVO_LAUNCH_TLP_L(SOA_, T_, BIN_, TILE_, true);                                         \
-        else NVO_LAUNCH_TLP_L(SOA_, T_, BIN_, TILE_, false);                                                  \
+#define NVO_LAUNCH_TLP_T(SOA_, T_, TILE_)                                                  \
+    do {                                                                                   \
+        if (live_list) NVO_LAUNCH_TLP_L(SOA_, T_, TILE_, true);                            \
+        else NVO_LAUNCH_TLP_L(SOA_, T_, TILE_, false);                                     \
     } while (0)
 #define NVO_LAUNCH_TLP(SOA_, T_)                                                           \
     do {                                                                                   \
-        if (st->bin_entries != kBinP) NVO_LAUNCH_TLP_B(SOA_, T_, kBinPSmall, 512);         \
-        else if (tile == 1024) NVO_LAUNCH_TLP_B(SOA_, T_, kBinP, 1024);                    \
-        else NVO_LAUNCH_TLP_B(SOA_, T_, kBinP, 512);                                       \
+        if (tile == 1024) NVO_LAUNCH_TLP_T(SOA_, T_, 1024);                                \
+        else NVO_LAUNCH_TLP_T(SOA_, T_, 512);                                              \
     } while (0)
     if (soa) NVO_DY_DISPATCH(NVO_LAUNCH_TLP, true); else NVO_DY_DISPATCH(NVO_LAUNCH_TLP, false);
 #undef NVO_LAUNCH_TLP
-#undef NVO_LAUNCH_TLP_B
+#undef NVO_LAUNCH_TLP_T
 #undef NVO_LAUNCH_TLP_L
     NVO_CHECK_LAUNCH();
     if (fork) NVO_CHECK_HIP(hipStreamWaitEvent(stream, st->ev_join, 0));  // join
@@ -3806,10 +3312,9 @@ int nvo_grid_bwd_launch(const NvoGridLevels& g, const NvoGridSlices* slices, hip
         // hit queue of the hashed levels' items (kHitCap): the wave rings sit behind the 32-bit accumulators
         uint32_t ring_off = 0u;
         {
-            static const bool hitq = [] { const char* e = getenv("NVO_GRID_HITQ"); return !e || atoi(e) != 0; }();
             bool any_hashed = false;
             for (uint32_t l = 0; l < g.n_levels; ++l) any_hashed = any_hashed || (((slices->level_mask >> l) & 1u) && g.hashed[l]);
-            if (hitq && any_hashed && slices->acc_bits == 32 && lds == 2 * AccFixed32::kEntries * sizeof(int) &&
+            if (any_hashed && slices->acc_bits == 32 && lds == 2 * AccFixed32::kEntries * sizeof(int) &&
                 lds + kHitRingBytes <= kLdsBwdBytes - 256) {
                 ring_off = (uint32_t)lds;
                 lds += kHitRingBytes;
@@ -3854,31 +3359,6 @@ int nvo_grid_bwd_launch(const NvoGridLevels& g, const NvoGridSlices* slices, hip
             }
 #undef NVO_LAUNCH_L1
         }
-        // slice codes of the hashed levels (k_slice_codes; see the coded scan of grid_bwd_item): one pre-pass over the
-        // positions instead of a cell + hash derivation on every slice visit
-        const uint16_t* d_codes = nullptr;
-        uint32_t code_levels = 0u;
-        {
-            // NVO_GRID_SLICE_CODES=1 (A/B; default OFF -- a measured negative, EXPERIMENTS 10.4: 201 -> 212 us on 1 M live
-            // samples, 97 -> 108 us with 60 % dead: a drained entry re-derives cell, hashes and weights from an uncoalesced
-            // position load, which costs what the 59 % of skipped visits save)
-            static const bool codes_env = [] { const char* e = getenv("NVO_GRID_SLICE_CODES"); return e && atoi(e) != 0; }();
-            if (codes_env && ring_off != 0u && dy_fmt != NVO_DY_FLOAT && N < (1u << 28)) {
-                for (uint32_t l = 0; l < g.n_levels; ++l) {
-                    const uint32_t size = g.offset[l + 1] - g.offset[l];
-                    if (((slices->level_mask >> l) & 1u) && g.hashed[l] && (size & (size - 1u)) == 0u && size >= 16384u &&
-                        size <= 8u * 16384u && g.resolution[l] + 1u < 16384u)
-                        code_levels |= 1u << l;
-                }
-            }
-            if (code_levels) {
-                const size_t bytes = sizeof(uint16_t) * (size_t)__builtin_popcount(code_levels) * N;
-                if (int rc = nvo_scratch_reserve(&slices->codes, bytes, stream, "grid_bwd slice codes")) return rc;
-                uint16_t* dc = static_cast<uint16_t*>(slices->codes.ptr);
-                NVO_LAUNCH(k_slice_codes, dim3(nvo_div_up(N, 256)), dim3(256), 0, stream, g, N, x, code_levels, dc);
-                d_codes = dc;
-            }
-        }
 #define NVO_LAUNCH_LDS(SOA_, T_)                                                              \
     do {                                                                                      \
         static bool attr_set = false; /* >64 KiB of dynamic LDS needs an explicit opt-in */   \
@@ -3890,7 +3370,7 @@ int nvo_grid_bwd_launch(const NvoGridLevels& g, const NvoGridSlices* slices, hip
         }                                                                                     \
         NVO_LAUNCH((k_grid_bwd_lds<SOA_, T_>), grid, block, lds, stream, g, N, x,     \
                            (const T_*)dy, grad, (const uint4*)slices->d_level, slices->d_l1, live, slices->nf_flag, slices->d_live_n, ring_off, \
-                           slices->ext_l1, slices->ext_blocks, slices->ext_l1_stride, d_codes, code_levels,         \
+                           slices->ext_l1, slices->ext_blocks, slices->ext_l1_stride,                                \
                            slices->ext_list ? 1024u : 4096u);                                                   \
     } while (0)
         if (soa) {

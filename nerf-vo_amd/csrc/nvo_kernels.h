@@ -32,7 +32,6 @@ struct NvoGridSlices {
     // was loaded and tested once per slice (25 slice scans for a proposal grid).
     bool compact_live = false;
     mutable NvoScratch live;              // [1 + N] uint32: count, then the live sample ids (grows with N; graph-safe)
-    mutable NvoScratch codes;             // [coded levels][N] uint16: slice codes of the hashed levels (k_slice_codes)
     // option grid_bwd_runs (set before create): the items of DENSE levels scan with run merging -- a lane takes 8
     // consecutive samples, sums the corner contributions in registers while the cell stays the same and goes to the LDS
     // accumulators once per run (consecutive samples are neighbours on a ray, so a coarse cell holds a run of them)
@@ -83,7 +82,7 @@ void nvo_grid_slices_zero_ranges(const NvoGridLevels& g, const NvoGridSlices* s,
 // level_mask: bit l set -> level l gets slice-owner work items (default: all levels); target_items: the
 // chunk counts are scaled until the launch has about this many work items
 int nvo_grid_slices_create(const NvoGridLevels& g, NvoGridSlices* s, uint32_t level_mask = 0xFFFFFFFFu,
-                           uint32_t target_items = 1024, bool env_items = true);
+                           uint32_t target_items = 1024);
 
 // Streamed backward (mode 3): levels with many 4K-entry bins go through a scatter of self-contained 12-byte pair records,
 // bin-sorted inside each tile, and a streaming accumulate into packed 2 x 32-bit LDS sums; the coarse levels keep
@@ -130,18 +129,17 @@ struct NvoGridStream {
     // gradient ranges, so they CAN run side by side (the former on this auxiliary stream, forked from / joined to the
     // caller's stream, also inside a graph capture).  Measured on the full step: 0.781 / 0.785 ms with the fork vs
     // 0.778 / 0.775 ms back to back -- the 512 slice-owner items already fill the CUs -- so the default is off
-    // (option grid_stream_overlap / NVO_GRID_STREAM_OVERLAP=1).
+    // (option grid_stream_overlap).
     bool overlap = false;
     // Record layout: every (tile, level) keeps its bin-sorted 12-byte pair records in a fixed region + a [bin][tile]
     // segment table; accumulate items are static (grid.hip).  Accumulators of the record pass: two 32-bit fixed-point sums
     // in ONE 64-bit word (one LDS atomic per record), 8192-entry bins, overflow-proof scale from per-(tile, bin) L1 bounds
     // the scatter delivers with its rank atomics (k_tl_scatter_p).  (Rounds 2-3 also carried a globally bin-sorted layout
     // with count / scan passes and 64-bit accumulators over 4096-entry bins: 0.769 vs 0.744 ms per step, removed.)
-    uint32_t bin_entries = 4096;      // (set by create)
     uint32_t dense_chunks = 8;        // tile-range chunks per bin of a streamed DENSE level (clustered samples)
     uint32_t* d_tl_items = nullptr;   // uint4 {bin, chunk | n_chunks << 16, streamed-level index | level << 8, slice}
     uint32_t n_tl_items = 0;
-    uint32_t n_tl_slots = 0;          // (packed form) persistent workgroups the balanced item list was laid out for; 0 = dealt
+    uint32_t n_tl_slots = 0;          // persistent workgroups the balanced item list was laid out for (set by create)
     hipStream_t aux = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool external_zero = false;  // see NvoGridSlices::external_zero
@@ -165,8 +163,8 @@ int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, 
                         void* dydx_half = nullptr, bool out_bf16 = false, const uint32_t* n_live = nullptr,
                         bool runs = false, int small_form = -1);
 // small_form: form of the small-grid forward (5-level grids whose two coarsest levels fit the LDS): -1 = the default
-// (NVO_GRID_FWD_SMALL, else the instruction-lean form), 0 = the generic kernel, 1 plain, 2 two samples per thread,
-// 3 software-pipelined, 4 instruction-lean + pipelined.  All forms produce the same bits.
+// (the instruction-lean form), 0 = the generic kernel, 1 plain, 4 instruction-lean + pipelined; anything else is an
+// error.  All forms produce the same bits.
 int nvo_grid_bwd_input_dydx_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, const void* dydx_half,
                                    const void* dy, int dy_fmt, bool soa, float* dx, bool zero_dx);
 int nvo_grid_bwd_launch(const NvoGridLevels& g, const NvoGridSlices* slices, hipStream_t stream,

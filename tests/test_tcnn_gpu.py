@@ -853,8 +853,9 @@ def test_double_backward_raises_like_upstream(device):
 @pytest.mark.parametrize("cfg", [PROP0, PROP1, MAIN], ids=["prop0", "prop1", "main"])
 def test_grid_forward_forms_are_bit_identical(device, cfg, dtype):
     """The level-major forward has several forms of ONE arithmetic (module option grid_fwd_small_form).  Proposal grids:
-    0 the first thread-per-(sample, level) kernel, 1 coarse levels from LDS, 3 software-pipelined, 4 instruction-lean (the
-    default).  Main grid: 0 the first kernel, anything else the instruction-lean one (the default).  Same fp32
+    0 the first thread-per-(sample, level) kernel, 1 coarse levels from LDS, 4 instruction-lean (the default).  Main grid:
+    the first kernel whatever the form; its run-walking form is the first one for 0 and the instruction-lean one otherwise.
+    Forms 2 and 3 no longer exist and the option rejects them.  Same fp32
     interpolation in the same order, one rounding: the outputs must agree bit for bit, on ray-coherent samples, on cells
     at the domain faces (the dense levels' wrap takes the lean forms' generic branch), on positions outside [0, 1]
     (memory-safe garbage in every form, the SAME garbage), and for batches that end inside a pass / a tile."""
@@ -868,6 +869,8 @@ def test_grid_forward_forms_are_bit_identical(device, cfg, dtype):
     m.set_option("bf16", int(dtype == "bf16"))
     with torch.no_grad():
         net.params.uniform_(-1, 1)
+    with pytest.raises(RuntimeError, match="grid_fwd_small_form"):
+        m.set_option("grid_fwd_small_form", 3)
     g = torch.Generator(device="cpu").manual_seed(5)
     for n, S in ((4096 * 96, 96), (1024 * 256 + 640, 256), (131 * 128, 96)):
         R = (n + S - 1) // S
@@ -884,7 +887,7 @@ def test_grid_forward_forms_are_bit_identical(device, cfg, dtype):
         x[72] = torch.tensor([-3.0, 7.0, 2.0])
         x = x.to(device)
         outs = {}
-        for form in (0, 1, 3, 4):
+        for form in (0, 1, 4):
             m.set_option("grid_fwd_small_form", form)
             with torch.no_grad():
                 y = net(x)
@@ -901,6 +904,6 @@ def test_grid_forward_forms_are_bit_identical(device, cfg, dtype):
             outs[("runs", form)] = y.view(torch.int16).cpu()
         m.set_option("grid_fwd_runs", 0)
         m.set_option("grid_fwd_small_form", -1)
-        for form in (0, 3, 4, ("runs", 1), ("runs", 4)):
+        for form in (0, 4, ("runs", 1), ("runs", 4)):
             diff = int((outs[form] != outs[1]).sum())
             assert diff == 0, f"form {form} differs from form 1 in {diff} of {outs[1].numel()} outputs (n={n})"

@@ -63,12 +63,7 @@ ngp)
     python3 $ROOT/tools/ngp_bench.py --steps 200 --profile --render-frames 3 --profile-render > $OUT/${R}_ngp_bench.txt 2> $OUT/${R}_ngp_bench.err
     grep -v "^{" $OUT/${R}_ngp_bench.txt | tail -45 ;;
 probes)
-    { for v in 1 3 4; do NVO_GRID_FWD_SMALL=$v python3 $ROOT/tools/probes/fwd_small_ab.py /tmp/ab_small.pt 2>&1 | grep -E "back to back|grid_fwd|identical"; done; } > $OUT/${R}_probe_fwd_small_forms.txt
-    { echo "--- NVO_GRID_FWD_LEAN=1 (form 4 = k_grid_fwd_lean with the aligned 8-byte pair on hashed levels; form 0 = k_grid_fwd, the default)";
-      NVO_GRID_FWD_LEAN=1 python3 $ROOT/tools/probes/fwd_main_ab.py 2>&1 | grep -E "form|identical"
-      echo "--- NVO_GRID_FWD_LEAN=1 NVO_GRID_FWD_PAIR=0 (plain 4-byte gathers in the lean form)"
-      NVO_GRID_FWD_LEAN=1 NVO_GRID_FWD_PAIR=0 python3 $ROOT/tools/probes/fwd_main_ab.py 2>&1 | grep -E "form 4"; } > $OUT/${R}_probe_fwd_main_forms.txt
-    { for v in 0 1; do NVO_GRID_SLICE_CODES=$v python3 $ROOT/tools/probes/bwd_codes_ab.py /tmp/ab_codes.pt 2>&1 | grep -E "grid_bwd|identical|saved"; done; } > $OUT/${R}_probe_bwd_slice_codes.txt
+    python3 $ROOT/tools/probes/fwd_small_ab.py 2>&1 | grep -E "back to back|grid_fwd|identical" > $OUT/${R}_probe_fwd_small_forms.txt
     $ROOT/tools/probes/launch_probe > $OUT/${R}_probe_launch_staging.txt 2>&1
     tail -n +1 $OUT/${R}_probe_*.txt | cut -c1-170 ;;
 lists)   # round 6: what a trained field's dead tiles buy (EngineConfig.sparse_backward), and what the probe costs where none are dead
@@ -92,7 +87,7 @@ lists)   # round 6: what a trained field's dead tiles buy (EngineConfig.sparse_b
     cat $OUT/${R}_probe_dead_tiles.txt; head -14 $OUT/${R}_trained_field_kernel_stats_sparse_auto.csv ;;
 phase)   # shader-clock shares of the grid kernels (an instrumented build: the product library is rebuilt afterwards)
     for v in 1 4; do
-        NVO_EXTRA_CXXFLAGS=-DNVO_GRID_PHASE NVO_GRID_FWD_SMALL=$v python3 $ROOT/tools/grid_phase.py --steps 60 --dynamic-loss-scale 2>&1 | grep -A8 "k_grid_fwd_small, per workgroup" | sed "s/^/[NVO_GRID_FWD_SMALL=$v] /"
+        NVO_EXTRA_CXXFLAGS=-DNVO_GRID_PHASE python3 $ROOT/tools/grid_phase.py --steps 60 --dynamic-loss-scale --fwd-small-form $v 2>&1 | grep -A8 "k_grid_fwd_small, per workgroup" | sed "s/^/[grid_fwd_small_form=$v] /"
     done > $OUT/${R}_grid_phase_fwd_small.txt
     python3 -c "import sys; sys.path.insert(0, '$ROOT'); import __graft_entry__ as g; g.build()" > /dev/null 2>&1
     cat $OUT/${R}_grid_phase_fwd_small.txt ;;

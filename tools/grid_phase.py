@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--keyframes", type=int, default=48)
     ap.add_argument("--mlp-dtype", default="f16")
     ap.add_argument("--dynamic-loss-scale", action="store_true")
+    ap.add_argument("--fwd-small-form", type=int, default=-1, choices=(-1, 0, 1, 4),
+                    help="module option grid_fwd_small_form of the proposal networks (-1 = the default form)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     n, H, W, R = a.keyframes, 240, 320, 4096
@@ -46,6 +48,8 @@ def main():
                "frames_depth": seq["frames_depth"]})
     eng = NerfactoEngine(EngineConfig(num_images=n, num_rays=R, mlp_dtype=a.mlp_dtype,
                                       dynamic_loss_scale=a.dynamic_loss_scale), dev)
+    for m in eng.prop_nets:
+        m.set_option("grid_fwd_small_form", a.fwd_small_form)
     raw = _lib.lib()
     if not hasattr(raw, "nvo_debug_grid_phase"):
         raise SystemExit("library was not built with -DNVO_GRID_PHASE (set NVO_EXTRA_CXXFLAGS for this run)")
