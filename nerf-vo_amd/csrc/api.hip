@@ -470,10 +470,13 @@ struct GridModule : nvo_module_s {
     uint32_t dydx_batch = 0;
     uint64_t dydx_bytes(uint32_t B) const { return nvo_round_up((uint64_t)g.n_levels * 3 * B * 4, 256); }
     // shared by the stand-alone encoding and NetworkWithInputEncoding (dydx: where in ITS ctx the block lives)
-    int fwd_encode(hipStream_t s, uint32_t B, const float* in, const void* table, void* out, bool soa, void* dydx) {
+    // density / density_ran: the network behind this encoding as the forward's epilogue (NvoGridDensity), where it qualifies
+    int fwd_encode(hipStream_t s, uint32_t B, const float* in, const void* table, void* out, bool soa, void* dydx,
+                   const NvoGridDensity* density = nullptr, bool* density_ran = nullptr) {
         dydx_valid = dydx != nullptr;
         dydx_batch = B;
-        return nvo_grid_fwd_launch(g, s, B, in, table, out, soa, nullptr, dydx, bf16, n_live, fwd_runs, fwd_small_form);
+        return nvo_grid_fwd_launch(g, s, B, in, table, out, soa, nullptr, dydx, bf16, n_live, fwd_runs, fwd_small_form,
+                                   density, density_ran);
     }
     int bwd_input(hipStream_t s, uint32_t B, const float* in, const void* table, const void* dout, bool soa,
                   float* din, const void* dydx) {
@@ -762,7 +765,15 @@ struct NwieModule : nvo_module_s {
     // (NVO_IO_GRID_FUSED) -- one launch, no feature round trip between two kernels.  Meant for grids whose tables fit
     // every XCD's L2 (the proposal networks: 1.5 MB): the stand-alone k_grid_fwd keeps a level's table on ONE XCD,
     // which a fused kernel cannot.  Bit-identical outputs.
+    // Value 2: the other way round -- the network is the EPILOGUE of the small-grid forward (NvoGridDensity: the grid kernel
+    // keeps its LDS levels and its pipeline and feeds the features it has just rounded to the matrix cores).  Taken for a
+    // 16-wide ReLU network with one hidden layer and a compact output behind a grid that qualifies for the lean
+    // small-grid forward, B a multiple of 16, no dy/dx; anything else runs the two kernels.  Bit-identical outputs.
     int fuse_encoding = 0;
+    // option "store_encoded" (default 1): 0 = the epilogue form does not store the features (inference; steps whose
+    // backward does not reach this network).  A backward on the ctx of such a forward is an error.
+    int store_encoded = 1;
+    const void* ctx_without_features = nullptr;  // ctx of the last forward that left the features out
     NvoGridLevels* d_levels = nullptr;  // device copy of enc->g for the fused kernel
 
     int fused_adam_range(uint64_t* first, uint64_t* n) override {
@@ -792,7 +803,29 @@ struct NwieModule : nvo_module_s {
         void* hidden = c + 2 * enc_bytes(B);
         const _Float16* p = (const _Float16*)params;
         void* dydx = enc->prepare_input_gradients ? c + dydx_offset(B) : nullptr;
-        if (fuse_encoding && !dydx && !enc->n_live && net->n_hidden == 1 && net->in_pad <= 32 && net->out_pad == 16) {
+        if (ctx_without_features == ctx) ctx_without_features = nullptr;
+        if (fuse_encoding == 2 && !dydx && compact_out && net->n_hidden == 1 && net->in_pad == 16 && net->width == 16 &&
+            net->out_pad == 16 && net->act == NVO_ACT_RELU && enc->n_out == 10 && (net->bf16 != 0) == (enc->bf16 != 0) &&
+            (B & 15u) == 0u) {
+            NvoGridDensity d;
+            d.weights = p;
+            d.output = out;
+            d.hidden = recompute_hidden ? nullptr : hidden;
+            d.out_act = net->out_act;
+            d.store_encoded = store_encoded;
+            bool ran = false;
+            if (int rc = enc->fwd_encode(s, B, in, p + net->n_params, encoded, true, nullptr, &d, &ran)) return rc;
+            if (!ran) {  // (the grid took another forward form: the features are stored, the network runs as a kernel of its own)
+                NvoMlpArgs a = net->make_args(B, encoded, NVO_IO_HALF2_SOA, enc->n_out, p, out, hidden);
+                a.compact_out = compact_out;
+                if (recompute_hidden) a.hidden = nullptr;
+                a.n_live = enc->n_live;
+                return nvo_mlp_fwd_launch(net->in_pad, net->width, net->n_hidden, net->out_pad, a, s);
+            }
+            if (!store_encoded) ctx_without_features = ctx;
+            return NVO_OK;
+        }
+        if (fuse_encoding == 1 && !dydx && !enc->n_live && net->n_hidden == 1 && net->in_pad <= 32 && net->out_pad == 16) {
             if (!d_levels) {  // (first call = an eager warm-up step, never under graph capture)
                 NVO_CHECK_HIP(hipMalloc((void**)&d_levels, sizeof(NvoGridLevels)));
                 NVO_CHECK_HIP(hipMemcpy(d_levels, &enc->g, sizeof(NvoGridLevels), hipMemcpyHostToDevice));
@@ -834,6 +867,8 @@ struct NwieModule : nvo_module_s {
     int bwd_on(hipStream_t s, hipStream_t sp, uint32_t B, const float* in, const void* params, const void* out,
                const void* dout, void* ctx, float* din, float* dparams) {
         NVO_REQUIRE(ctx != nullptr, "NetworkWithInputEncoding.bwd needs the ctx of the matching fwd");
+        NVO_REQUIRE(ctx != ctx_without_features,
+                    "NetworkWithInputEncoding.bwd: the forward on this ctx ran with store_encoded = 0 and stored no features");
         char* c = (char*)ctx;
         void* encoded = c;
         void* dencoded = c + enc_bytes(B);
@@ -940,8 +975,13 @@ struct NwieModule : nvo_module_s {
             net->bf16 = value != 0;
             return enc->set_option(key, value);
         }
-        if (!strcmp(key, "fuse_encoding")) {
-            fuse_encoding = value != 0;
+        if (!strcmp(key, "fuse_encoding")) {  // 0 two kernels | 1 grid inside the MLP's operand load | 2 MLP as the grid's epilogue
+            NVO_REQUIRE(value >= 0 && value <= 2, "fuse_encoding: 0, 1 or 2 (got %lld)", (long long)value);
+            fuse_encoding = (int)value;
+            return NVO_OK;
+        }
+        if (!strcmp(key, "store_encoded")) {
+            store_encoded = value != 0;
             return NVO_OK;
         }
         if (!strcmp(key, "deterministic")) {  // network weight gradient AND hash-grid gradient bitwise reproducible

@@ -23,6 +23,8 @@
 //                                    LDS, a thread per sample.  The readable statement of the small-grid arithmetic
 //                                    (option grid_fwd_small_form = 1); the lean forms are pinned to it bit for bit.
 //      - k_grid_fwd_small_lean:      the same, instruction-lean and software-pipelined: the default for small grids.
+//                                    <.., DENS> (and of k_grid_fwd_small_runs_lean): with the proposal density network as
+//                                    the epilogue -- NvoGridDensity, module option fuse_encoding = 2.
 //      - k_grid_fwd_runs_lean,
 //        k_grid_fwd_small_runs_lean: run-walking forms (option grid_fwd_runs, inference: a thread walks four consecutive
 //                                    samples and gathers only where the cell changes), with k_grid_fwd_runs and
@@ -45,6 +47,14 @@
 //      - k_grid_bwd_input_dydx:      streams the d(out)/d(cell) block a forward with prepare_input_gradients stored.
 //      - k_grid_bwd_input (+ k_sum_levels): gathers the corners again; per-level partials, no float atomics.
 #include "nvo_kernels.h"
+
+// the fully fused MLP's device functions for both 16-bit element types (the density epilogue of the small-grid forward)
+#define NVO_MLP_BF16 0
+#include "mlp_dev.h"
+#undef NVO_MLP_BF16
+#define NVO_MLP_BF16 1
+#include "mlp_dev.h"
+#undef NVO_MLP_BF16
 
 #include <math.h>
 #include <string.h>
@@ -90,7 +100,7 @@ uint32_t nvo_grid_levels_init(NvoGridLevels* g, uint32_t n_levels, uint32_t n_fe
 // SHARES, not the totals).  Slots: [0..6] k_tl_accumulate_p (zero+L1, records, barrier, flush, end barrier, hashed items,
 // dense items); [8..14] k_tl_scatter_p (loads+max, index+rank, barrier, bin scan, stage, copy-out, workgroups);
 // [16..20] slice-owner dense items, [24..28] hashed items (zero, scan, barrier, flush, items); [32..37] k_grid_fwd_small
-// (staging, loop, issue, LDS levels, consume, workgroups).
+// (staging, loop, issue, LDS levels, consume, workgroups); [38] the density epilogue of k_grid_fwd_small_lean<.., DENS>.
 #ifdef NVO_GRID_PHASE
 __device__ unsigned long long nvo_grid_phase_cycles[48];
 #define GP_CLK(v) const unsigned long long v = __builtin_readcyclecounter()
@@ -602,17 +612,104 @@ __device__ __forceinline__ uint32_t lean_interp(const float (&w)[4][2], const ui
     return lean_cvt16x2<BF>(r0, r1);
 }
 
-template <int NLDS, int NG, uint32_t HMASK, bool BF>
+// ---- DENSITY EPILOGUE of the lean small-grid forwards (template parameter DENS; NvoGridDensity) ----------------------
+// The proposal networks are this grid followed by a 10 -> 16 -> 1 MLP.  As two kernels every sample's five feature pairs
+// go to memory, the grid kernel drains, and k_mlp_fwd<16,16,1,16> stages 1 KB of weights to read 20 bytes back and run two
+// matrix instructions per 16 samples.  Here the wave that has just rounded its samples' features feeds them to the same
+// device functions (mlp_dev.h: layer_mm<16,16>, pack_act, layer_mm<16,16>, pack_act -- the operand order of k_mlp_fwd)
+// and stores column 0; the feature store itself becomes optional (NvoGridDensity::store_encoded).
+// What it takes is a re-layout: a lane holds ALL features of ONE sample, the B operand of the matrix instruction wants
+// lane m + 16 g to hold features 4g .. 4g+3 (the pairs of levels 2g, 2g+1) of sample m of a 16-sample tile.  With
+// E_g = the register of level 2g (E_3 = 0: features 12..15 are the pad) and the wave's four 16-lane rows as tiles, the
+// operand of tile t is X_t[row g] = E_g[row t]: a 4 x 4 transpose of (register, row), which gfx950 does in four vector
+// instructions (v_permlane32_swap exchanges the upper rows of one register with the lower rows of another,
+// v_permlane16_swap the odd rows with the even rows) -- no LDS patch (the second proposal grid's LDS levels leave 16 KB of
+// the CU's 160 KB: 1024 samples x 20 bytes do not fit) and none of the 20 ds_bpermute + 20 selects of the gather form.
+// Which 16 samples share a tile is free: a column of the product depends on its own column of B alone, so the outputs are
+// the bits k_mlp_fwd computes whatever the grouping.
+template <bool BF> struct DensDev;
+#define NVO_DENS_DEV(BF_, NS_)                                                                                          \
+    template <> struct DensDev<BF_> {                                                                                   \
+        typedef NS_::T T;                                                                                               \
+        typedef NS_::T4 T4;                                                                                             \
+        typedef NS_::f4 f4;                                                                                             \
+        typedef NS_::WFrag<16, 16> W;                                                                                   \
+        typedef NS_::RowStage<16, 16> Stage;                                                                            \
+        static __device__ __forceinline__ void mm(const W& w, const T4 (&in)[1], f4 (&acc)[1]) { NS_::layer_mm<16, 16>(w, in, acc); } \
+        static __device__ __forceinline__ T4 pack(int act, f4 v) { return NS_::pack_act(act, v); }                      \
+    }
+NVO_DENS_DEV(false, nvo_mlp_dev_f16);
+NVO_DENS_DEV(true, nvo_mlp_dev_bf16);
+#undef NVO_DENS_DEV
+constexpr uint32_t kDensStageBytes = 2u * 16u * (16u + 4u) * 2u;  // both weight matrices, RowStage's row stride: 1280 B
+
+// the workgroup's copy of the two 16 x 16 matrices (wave 0 stages; the caller's barrier publishes it)
+template <bool BF>
+__device__ __forceinline__ void dens_stage(const NvoGridDensity& d, void* stage) {
+    using D = DensDev<BF>;
+    if (threadIdx.x < 64u) {  // (wave-uniform; 64 lanes x 8 bytes = one matrix)
+        const typename D::T* W = static_cast<const typename D::T*>(d.weights);
+        typename D::Stage s0, s1;
+        s0.issue(W);
+        s1.issue(W + 16 * 16);
+        s0.store(static_cast<typename D::T*>(stage));
+        s1.store(static_cast<typename D::T*>(stage) + D::Stage::kHalfs);
+    }
+}
+
+// v[g] = one 32-bit register per row group g; on return v[t][row g] = what v[g] held in row t.  ALL 64 lanes active.
+__device__ __forceinline__ void dens_rows_transpose(uint32_t (&v)[4]) {
+    const auto a = __builtin_amdgcn_permlane32_swap(v[0], v[2], false, false);
+    const auto b = __builtin_amdgcn_permlane32_swap(v[1], v[3], false, false);
+    const auto c = __builtin_amdgcn_permlane16_swap(a[0], b[0], false, false);
+    const auto e = __builtin_amdgcn_permlane16_swap(a[1], b[1], false, false);
+    v[0] = c[0]; v[1] = c[1]; v[2] = e[0]; v[3] = e[1];
+}
+
+// 64 samples, one per lane (r[l] = the lane's feature pair of level l, rounded as it is stored), through the network.
+// Tile t = the samples of lanes 16 t .. 16 t + 15; out[t] = column 0 of sample 16 t + (lane & 15), valid where lane < 16;
+// h[t] = the hidden activations 4g .. 4g+3 (g = lane >> 4) of that sample, valid in every lane.  ALL 64 lanes active.
+template <bool BF>
+__device__ __forceinline__ void dens_wave(const uint32_t (&r)[5], const void* stage, int lane, int out_act,
+                                          typename DensDev<BF>::T (&out)[4], typename DensDev<BF>::T4 (&h)[4]) {
+    using D = DensDev<BF>;
+    uint32_t ev[4] = {r[0], r[2], r[4], 0u}, od[4] = {r[1], r[3], 0u, 0u};
+    dens_rows_transpose(ev);
+    dens_rows_transpose(od);
+    typename D::W w0, wl;
+    w0.load_staged(static_cast<const typename D::T*>(stage), lane);
+    wl.load_staged(static_cast<const typename D::T*>(stage) + D::Stage::kHalfs, lane);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const uint2 xx = make_uint2(ev[t], od[t]);
+        typename D::T4 x[1];
+        __builtin_memcpy(&x[0], &xx, sizeof(xx));
+        typename D::f4 acc[1], o[1];
+        D::mm(w0, x, acc);
+        typename D::T4 hh[1] = {D::pack((int)NVO_ACT_RELU, acc[0])};
+        h[t] = hh[0];
+        D::mm(wl, hh, o);
+        out[t] = D::pack(out_act, o[0])[0];
+    }
+}
+
+template <int NLDS, int NG, uint32_t HMASK, bool BF, bool DENS = false>
 __global__ void __launch_bounds__(kSmallBlock)
 k_grid_fwd_small_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const __half2* __restrict__ table,
-                      __half2* __restrict__ out, uint32_t per_block) {
+                      __half2* __restrict__ out, uint32_t per_block, NvoGridDensity dens, const uint32_t* __restrict__ n_live) {
+    static_assert(!DENS || NLDS + NG == 5, "the density epilogue takes five levels");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_tab[];
     const unsigned char* __restrict__ tab8 = reinterpret_cast<const unsigned char*>(table);
     const unsigned char* __restrict__ x8 = reinterpret_cast<const unsigned char*>(x);
     unsigned char* __restrict__ o8 = reinterpret_cast<unsigned char*>(out);
     const uint32_t first = blockIdx.x * per_block;
-    const uint32_t last = min(N, first + per_block);
+    uint32_t n_rows = N;  // (DENS: whole 16-sample tiles up to the rows in use, as k_mlp_fwd; N stays the features' stride)
+    if constexpr (DENS) {
+        if (n_live) n_rows = min(N, (*n_live + 15u) & ~15u);
+    }
+    const uint32_t last = min(n_rows, first + per_block);
     if (first >= last) return;  // (uniform)
+    const bool store_enc = !DENS || dens.store_encoded != 0;  // (uniform)
     GP_CLK(gl0);
     const uint32_t n_pass = (last - first + kSmallBlock - 1u) / kSmallBlock;
     const uint32_t wave_first = first + (threadIdx.x & ~63u);  // first sample of this wave in pass 0
@@ -721,7 +818,10 @@ k_grid_fwd_small_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, 
 #pragma unroll
         for (int k = 0; k < kStageMax; ++k) dst[min(threadIdx.x + (uint32_t)k * kSmallBlock, n4 - 1u)] = st[k];
     }
+    const uint32_t* const dens_w = lds_tab + g.offset[NLDS];  // (DENS) the network's weights, behind the LDS levels
+    if constexpr (DENS) dens_stage<BF>(dens, lds_tab + g.offset[NLDS]);
 #ifdef NVO_GRID_PHASE
+    unsigned long long gl_epi = 0;
     GP_CLK(gls);
     if (threadIdx.x == 0) GP_ADD(34, gls - gl0);  // (staging alone, before the first pass's index arithmetic)
 #endif
@@ -736,7 +836,8 @@ k_grid_fwd_small_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, 
         if (wave_first + pass * kSmallBlock >= last) break;  // (wave-uniform: nothing of this wave is left; no barrier below)
         const uint32_t i = first + pass * kSmallBlock + threadIdx.x;
         const Pos p1 = load_pos(min(pass + 1u, n_pass - 1u));
-        const bool live = i < last;
+        const bool live = i < last && store_enc;  // (this lane stores its features)
+        uint32_t rr[DENS ? NLDS + NG : 1];    // (DENS) the sample's feature pairs, as stored
         // ---- LDS levels while the gathers fly
 #pragma unroll
         for (int l = 0; l < NLDS; ++l) {
@@ -765,6 +866,7 @@ k_grid_fwd_small_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, 
             lean_weights(c, w);
             const uint32_t r = lean_interp<BF>(w, even, odd);
             if (live) *reinterpret_cast<uint32_t*>(o8 + (((uint32_t)l * N + i) << 2)) = r;
+            if constexpr (DENS) rr[l] = r;
         }
         // ---- consume this pass's gathers
 #pragma unroll
@@ -790,6 +892,31 @@ k_grid_fwd_small_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, 
             lean_weights(cg[q], w);
             const uint32_t r = lean_interp<BF>(w, even, odd);
             if (live) *reinterpret_cast<uint32_t*>(o8 + (((uint32_t)(NLDS + q) * N + i) << 2)) = r;
+            if constexpr (DENS) rr[NLDS + q] = r;
+        }
+        // ---- (DENS) the network on this wave's 64 samples, while nothing of the gathers is live in registers
+        if constexpr (DENS) {
+            GP_CLK(ge0);
+            using D = DensDev<BF>;
+            const int lane = (int)(threadIdx.x & 63u);
+            typename D::T dv[4];
+            typename D::T4 dh[4];
+            dens_wave<BF>(rr, dens_w, lane, dens.out_act, dv, dh);
+            const uint32_t row0 = wave_first + pass * kSmallBlock + (uint32_t)(lane & 15);  // (tile t: + 16 t)
+            typename D::T* const dout = static_cast<typename D::T*>(dens.output);
+#pragma unroll
+            for (uint32_t t = 0; t < 4; ++t)
+                if (lane < 16 && row0 + 16u * t < last) dout[row0 + 16u * t] = dv[t];  // 16 lanes -> 32 contiguous bytes
+            if (dens.hidden) {  // (uniform; [N][16], what k_mlp_fwd stores unless the backward recomputes it)
+                typename D::T* const hs = static_cast<typename D::T*>(dens.hidden) + 4 * (lane >> 4);
+#pragma unroll
+                for (uint32_t t = 0; t < 4; ++t)
+                    if (row0 + 16u * t < last) *reinterpret_cast<typename D::T4*>(hs + (size_t)(row0 + 16u * t) * 16) = dh[t];
+            }
+#ifdef NVO_GRID_PHASE
+            GP_CLK(ge1);
+            gl_epi += ge1 - ge0;
+#endif
         }
         // ---- next pass's gathers
         if (wave_first + (pass + 1u) * kSmallBlock < last) issue(p1);  // (wave-uniform)
@@ -798,7 +925,7 @@ k_grid_fwd_small_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, 
 #ifdef NVO_GRID_PHASE
     if (threadIdx.x == 0) {  // (slots of k_grid_fwd_small: staging [+ the first pass's gather issue here], sample loop, workgroups)
         GP_CLK(gl2);
-        GP_ADD(32, gl1 - gl0); GP_ADD(33, gl2 - gl1); GP_ADD(37, 1);
+        GP_ADD(32, gl1 - gl0); GP_ADD(33, gl2 - gl1); GP_ADD(37, 1); GP_ADD(38, gl_epi);  // ([38]: the density epilogue)
     }
 #endif
 }
@@ -1042,11 +1169,16 @@ k_grid_fwd_runs_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, c
 // 8-byte pair around corner px (+ corner px + 1 for odd px, two lane predicates steering every select), 32-bit byte
 // offsets against scalar bases, packed weight products, and nothing computed from a loaded value next to its load.
 // Level by level (the raw gathers of four samples of one level are 48 registers).  Bit-identical to k_grid_fwd_small.
-template <int NLDS, int NG, uint32_t HMASK, bool BF>
+// DENS: the density epilogue (see k_grid_fwd_small_lean).  A lane holds four consecutive samples here, so the wave runs
+// the epilogue once per run position s with tile (t, s) = sample s of the lanes of row t, and a lane of row 0 ends up
+// with the outputs of four consecutive samples per t: one 8-byte store.  The matrix and lane-swap instructions need the
+// whole wave, so the sample loop of this form is wave-uniform (a lane past the end re-reads the last run and stores nothing).
+template <int NLDS, int NG, uint32_t HMASK, bool BF, bool DENS = false>
 __global__ void __launch_bounds__(kSmallBlock)
 k_grid_fwd_small_runs_lean(NvoGridLevels g, uint32_t N, const float* __restrict__ x, const __half2* __restrict__ table,
-                           __half2* __restrict__ out, uint32_t per_block) {
+                           __half2* __restrict__ out, uint32_t per_block, NvoGridDensity dens, const uint32_t* __restrict__ n_live) {
     constexpr int RUN = 4;
+    static_assert(!DENS || NLDS + NG == 5, "the density epilogue takes five levels");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_tab[];
     const unsigned char* __restrict__ tab8 = reinterpret_cast<const unsigned char*>(table);
     unsigned char* __restrict__ o8 = reinterpret_cast<unsigned char*>(out);
@@ -1060,9 +1192,19 @@ k_grid_fwd_small_runs_lean(NvoGridLevels g, uint32_t N, const float* __restrict_
 #pragma unroll
         for (int k = 0; k < kStageMax; ++k) dst[min(threadIdx.x + (uint32_t)k * kSmallBlock, n4 - 1u)] = st[k];
     }
+    const uint32_t* const dens_w = lds_tab + g.offset[NLDS];  // (DENS) the network's weights, behind the LDS levels
+    if constexpr (DENS) dens_stage<BF>(dens, lds_tab + g.offset[NLDS]);
     __syncthreads();
     const uint32_t first = blockIdx.x * per_block;
-    const uint32_t last = min(N, first + per_block);  // (both multiples of RUN)
+    uint32_t n_rows = N;
+    if constexpr (DENS) {
+        if (n_live) n_rows = min(N, (*n_live + 15u) & ~15u);
+        if (first >= n_rows) return;  // (uniform, behind the only barrier)
+    }
+    const uint32_t last = min(n_rows, first + per_block);  // (both multiples of RUN)
+    const bool store_enc = !DENS || dens.store_encoded != 0;  // (uniform)
+    bool live = true;                    // (DENS) this lane's run exists
+    uint32_t rr[DENS ? NLDS + NG : 1][RUN];  // (DENS) the run's feature pairs, as stored
     auto lds_level = [&](int l, const float (&p)[RUN * 3], uint32_t i0) {
         const uint32_t off = g.offset[l], size = g.offset[l + 1] - off, res = g.resolution[l];
         const uint32_t res2 = res * res;
@@ -1091,10 +1233,17 @@ k_grid_fwd_small_runs_lean(NvoGridLevels g, uint32_t N, const float* __restrict_
             float w[4][2];
             lean_weights(c, w);
             r[s] = lean_interp<BF>(w, even, odd);
+            if constexpr (DENS) rr[l][s] = r[s];
         }
-        *reinterpret_cast<uint4*>(o8 + (((uint32_t)l * N + i0) << 2)) = make_uint4(r[0], r[1], r[2], r[3]);
+        if (live && store_enc) *reinterpret_cast<uint4*>(o8 + (((uint32_t)l * N + i0) << 2)) = make_uint4(r[0], r[1], r[2], r[3]);
     };
-    for (uint32_t i0 = first + threadIdx.x * RUN; i0 < last; i0 += kSmallBlock * RUN) {
+    const uint32_t lane_off = DENS ? (threadIdx.x & 63u) * RUN : 0u;  // (DENS: the loop ends with the wave's FIRST lane)
+    for (uint32_t ib = first + threadIdx.x * RUN; ib - lane_off < last; ib += kSmallBlock * RUN) {
+        uint32_t i0 = ib;
+        if constexpr (DENS) {
+            live = ib < last;
+            i0 = min(ib, last - RUN);
+        }
         float p[RUN * 3];
         {
             const float4* __restrict__ xp = reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(x) + i0 * 12u);
@@ -1159,8 +1308,9 @@ k_grid_fwd_small_runs_lean(NvoGridLevels g, uint32_t N, const float* __restrict_
                     }
                 }
             }
-            // an LDS level while the gathers fly
-            if (q < NLDS) lds_level(q, p, i0);
+            // an LDS level while the gathers fly (DENS: behind the last global level -- this level's features would have to
+            // stay in registers beside the gathers of the others, 8 more than the 128 a wave of this workgroup may hold)
+            if (q < NLDS && !DENS) lds_level(q, p, i0);
             uint32_t even[4] = {0u, 0u, 0u, 0u}, odd[4] = {0u, 0u, 0u, 0u};
             uint32_t r[RUN];
 #pragma unroll
@@ -1187,10 +1337,43 @@ k_grid_fwd_small_runs_lean(NvoGridLevels g, uint32_t N, const float* __restrict_
                 lean_weights(c[s], w);
                 r[s] = lean_interp<BF>(w, even, odd);
             }
-            *reinterpret_cast<uint4*>(o8 + (((uint32_t)level * N + i0) << 2)) = make_uint4(r[0], r[1], r[2], r[3]);
+            if (live && store_enc) *reinterpret_cast<uint4*>(o8 + (((uint32_t)level * N + i0) << 2)) = make_uint4(r[0], r[1], r[2], r[3]);
+            if constexpr (DENS) {
+#pragma unroll
+                for (int s = 0; s < RUN; ++s) rr[level][s] = r[s];
+            }
         }
 #pragma unroll
-        for (int l = NG; l < NLDS; ++l) lds_level(l, p, i0);  // (more LDS levels than global ones: the rest)
+        for (int l = DENS ? 0 : NG; l < NLDS; ++l) lds_level(l, p, i0);  // (more LDS levels than global ones: the rest)
+        if constexpr (DENS) {
+            using D = DensDev<BF>;
+            const int lane = (int)(threadIdx.x & 63u);
+            const uint32_t wave0 = ib - lane_off;  // first sample of the wave's 256 in this trip
+            // tile (t, s), column m = lane & 15: sample wave0 + RUN (16 t + m) + s
+            const uint32_t row0 = wave0 + (uint32_t)RUN * (uint32_t)(lane & 15);
+            typename D::T dv[RUN][4];
+#pragma unroll
+            for (int s = 0; s < RUN; ++s) {
+                const uint32_t rs[5] = {rr[0][s], rr[1][s], rr[2][s], rr[3][s], rr[4][s]};
+                typename D::T4 dh[4];
+                dens_wave<BF>(rs, dens_w, lane, dens.out_act, dv[s], dh);
+                if (dens.hidden) {  // (uniform)
+                    typename D::T* const hs = static_cast<typename D::T*>(dens.hidden) + 4 * (lane >> 4);
+#pragma unroll
+                    for (uint32_t t = 0; t < 4; ++t) {
+                        const uint32_t row = row0 + (uint32_t)RUN * 16u * t + (uint32_t)s;
+                        if (row < last) *reinterpret_cast<typename D::T4*>(hs + (size_t)row * 16) = dh[t];
+                    }
+                }
+            }
+            typename D::T* const dout = static_cast<typename D::T*>(dens.output);
+#pragma unroll
+            for (uint32_t t = 0; t < 4; ++t) {
+                const uint32_t row = row0 + (uint32_t)RUN * 16u * t;
+                const typename D::T4 v4 = {dv[0][t], dv[1][t], dv[2][t], dv[3][t]};
+                if (lane < 16 && row < last) *reinterpret_cast<typename D::T4*>(dout + row) = v4;  // 16 lanes -> 128 contiguous bytes
+            }
+        }
     }
 }
 
@@ -2726,7 +2909,10 @@ static uint32_t grid_fwd_plan_build(const NvoGridLevels& g, uint32_t tiles, Grid
 
 int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, const float* x,
                         const void* table_half, void* out_half, bool soa, uint32_t* indices, void* dydx_half,
-                        bool out_bf16, const uint32_t* n_live, bool runs, int small_form) {
+                        bool out_bf16, const uint32_t* n_live, bool runs, int small_form, const NvoGridDensity* density,
+                        bool* density_ran) {
+    NVO_REQUIRE(!density || density_ran, "grid: the density epilogue reports through density_ran");
+    if (density_ran) *density_ran = false;
     if (N == 0) return NVO_OK;
     NVO_REQUIRE(g.n_features == 2, "grid: only n_features_per_level == 2 is supported (got %u)",
                 g.n_features);
@@ -2739,7 +2925,16 @@ int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, 
     NVO_REQUIRE(small_form == -1 || small_form == 0 || small_form == 1 || small_form == 4,
                 "grid: small-grid forward form %d (-1 default, 0 generic, 1 plain, 4 instruction-lean)", small_form);
     const int small_env = small_form >= 0 ? small_form : kSmallFormDefault;  // (module option grid_fwd_small_form: tests, A/B)
-    if (small_env && soa && !indices && !dydx_half && !n_live && g.n_levels == 5 && !g.hashed[0] && !g.hashed[1] &&
+    // the density epilogue exists in the lean forms; its 1280 bytes of staged weights sit behind the LDS levels (a CU has
+    // 160 KiB, one 1024-thread workgroup is resident either way), and its tiles are whole: N a multiple of 16
+    const uint32_t hm5 = (g.hashed[2] ? 1u : 0u) | (g.hashed[3] ? 2u : 0u) | (g.hashed[4] ? 4u : 0u);
+    const bool lean_ok = small_env >= 4 && (hm5 == 6u || hm5 == 7u || hm5 == 4u) && (uint64_t)N * 20u < (1ull << 32) &&
+                         g.resolution[0] <= 4096u && g.resolution[1] <= 4096u && g.resolution[2] <= 4096u;
+    const bool dens_shape = density && lean_ok && (N & 15u) == 0u && (size_t)g.offset[2] * 4 + kDensStageBytes <= 160 * 1024 &&
+                            (((uintptr_t)density->weights) & 7u) == 0u && (((uintptr_t)density->output) & 7u) == 0u &&
+                            (((uintptr_t)density->hidden) & 7u) == 0u;
+    const NvoGridDensity no_dens = {nullptr, nullptr, nullptr, 0, 1};
+    if (small_env && soa && !indices && !dydx_half && (!n_live || dens_shape) && g.n_levels == 5 && !g.hashed[0] && !g.hashed[1] &&
         (size_t)g.offset[2] * 4 <= 152 * 1024 && (g.offset[2] & 3u) == 0u && (((uintptr_t)table_half) & 15u) == 0u) {
         static const uint32_t n_cus = [] {
             int dev = 0, n = 256;
@@ -2753,7 +2948,8 @@ int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, 
                                               152 * 1024));
             attr_set = true;
         }
-        if (runs && (N & 3u) == 0u && (((uintptr_t)x) & 15u) == 0u && (((uintptr_t)out_half) & 15u) == 0u) {
+        // (the run-walking form has no lean kernel for hm5 == 4: with the epilogue asked for, such a grid takes the lean form below)
+        if (runs && (N & 3u) == 0u && (((uintptr_t)x) & 15u) == 0u && (((uintptr_t)out_half) & 15u) == 0u && !(dens_shape && hm5 == 4u)) {
             // option "grid_fwd_runs" (inference: 8 M samples per chunk -- 175 -> 158 us; on a training batch of 0.4-1 M
             // samples a 1024-thread workgroup of four-sample runs has one pass or less to do and loses 8 us)
             static bool attr_runs = false;
@@ -2763,24 +2959,31 @@ int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, 
                 attr_runs = true;
             }
             const uint32_t per_block = (uint32_t)nvo_round_up(nvo_div_up(N, n_cus), kSmallBlock * 4);
-            const uint32_t hm = (g.hashed[2] ? 1u : 0u) | (g.hashed[3] ? 2u : 0u) | (g.hashed[4] ? 4u : 0u);
-            if (small_env >= 4 && (hm == 6u || hm == 7u) && (uint64_t)N * 20u < (1ull << 32) && g.resolution[0] <= 4096u &&
-                g.resolution[1] <= 4096u && g.resolution[2] <= 4096u) {
-#define NVO_LAUNCH_RL(HM_, BF_)                                                                                           \
+            const uint32_t hm = hm5;
+            if (lean_ok && (hm == 6u || hm == 7u)) {
+#define NVO_LAUNCH_RL(HM_, BF_, DENS_)                                                                                    \
     do {                                                                                                                   \
         static bool attr_rl = false;                                                                                       \
         if (!attr_rl) {                                                                                                    \
-            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_grid_fwd_small_runs_lean<2, 3, HM_, BF_>,                     \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));                    \
+            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_grid_fwd_small_runs_lean<2, 3, HM_, BF_, DENS_>,              \
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024 + kDensStageBytes));  \
             attr_rl = true;                                                                                                \
         }                                                                                                                  \
-        NVO_LAUNCH((k_grid_fwd_small_runs_lean<2, 3, HM_, BF_>), dim3(nvo_div_up(N, per_block)), dim3(kSmallBlock), lds,   \
-                   stream, g, N, x, (const __half2*)table_half, (__half2*)out_half, per_block);                            \
+        NVO_LAUNCH((k_grid_fwd_small_runs_lean<2, 3, HM_, BF_, DENS_>), dim3(nvo_div_up(N, per_block)), dim3(kSmallBlock), \
+                   lds + (DENS_ ? kDensStageBytes : 0u), stream, g, N, x, (const __half2*)table_half, (__half2*)out_half,  \
+                   per_block, DENS_ ? *density : no_dens, n_live);                                                         \
     } while (0)
-                if (hm == 6u) { if (out_bf16) NVO_LAUNCH_RL(6u, true); else NVO_LAUNCH_RL(6u, false); }
-                else { if (out_bf16) NVO_LAUNCH_RL(7u, true); else NVO_LAUNCH_RL(7u, false); }
+#define NVO_LAUNCH_RL_D(HM_, BF_)                                                                                         \
+    do {                                                                                                                   \
+        if (dens_shape) NVO_LAUNCH_RL(HM_, BF_, true);                                                                     \
+        else NVO_LAUNCH_RL(HM_, BF_, false);                                                                               \
+    } while (0)
+                if (hm == 6u) { if (out_bf16) NVO_LAUNCH_RL_D(6u, true); else NVO_LAUNCH_RL_D(6u, false); }
+                else { if (out_bf16) NVO_LAUNCH_RL_D(7u, true); else NVO_LAUNCH_RL_D(7u, false); }
+#undef NVO_LAUNCH_RL_D
 #undef NVO_LAUNCH_RL
                 NVO_CHECK_LAUNCH();
+                if (dens_shape) *density_ran = true;
                 return NVO_OK;
             }
             NVO_LAUNCH((k_grid_fwd_small_runs<2, 3>), dim3(nvo_div_up(N, per_block)), dim3(kSmallBlock), lds, stream, g, N, x,
@@ -2788,28 +2991,35 @@ int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, 
             NVO_CHECK_LAUNCH();
             return NVO_OK;
         }
-        const uint32_t hmask = (g.hashed[2] ? 1u : 0u) | (g.hashed[3] ? 2u : 0u) | (g.hashed[4] ? 4u : 0u);
-        if (small_env >= 4 && (hmask == 6u || hmask == 7u || hmask == 4u) && (uint64_t)N * 20u < (1ull << 32) &&
-            g.resolution[0] <= 4096u && g.resolution[1] <= 4096u && g.resolution[2] <= 4096u) {
+        const uint32_t hmask = hm5;
+        if (lean_ok) {
             // the instruction-lean form: wave-granular shares (a workgroup's last pass may be partly empty: its idle waves leave)
             const uint32_t per_lean = (uint32_t)nvo_round_up(nvo_div_up(N, n_cus), 64u);
             const dim3 gl(nvo_div_up(N, per_lean));
-#define NVO_LAUNCH_LEAN(HM_, BF_)                                                                                          \
+#define NVO_LAUNCH_LEAN(HM_, BF_, DENS_)                                                                                   \
     do {                                                                                                                   \
         static bool attr_lean = false;                                                                                     \
         if (!attr_lean) {                                                                                                  \
-            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_grid_fwd_small_lean<2, 3, HM_, BF_>,                          \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));                    \
+            NVO_CHECK_HIP(hipFuncSetAttribute((const void*)k_grid_fwd_small_lean<2, 3, HM_, BF_, DENS_>,                   \
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024 + kDensStageBytes));  \
             attr_lean = true;                                                                                              \
         }                                                                                                                  \
-        NVO_LAUNCH((k_grid_fwd_small_lean<2, 3, HM_, BF_>), gl, dim3(kSmallBlock), lds, stream, g, N, x,                   \
-                   (const __half2*)table_half, (__half2*)out_half, per_lean);                                              \
+        NVO_LAUNCH((k_grid_fwd_small_lean<2, 3, HM_, BF_, DENS_>), gl, dim3(kSmallBlock),                                  \
+                   lds + (DENS_ ? kDensStageBytes : 0u), stream, g, N, x, (const __half2*)table_half, (__half2*)out_half,  \
+                   per_lean, DENS_ ? *density : no_dens, n_live);                                                          \
     } while (0)
-            if (hmask == 6u) { if (out_bf16) NVO_LAUNCH_LEAN(6u, true); else NVO_LAUNCH_LEAN(6u, false); }
-            else if (hmask == 7u) { if (out_bf16) NVO_LAUNCH_LEAN(7u, true); else NVO_LAUNCH_LEAN(7u, false); }
-            else { if (out_bf16) NVO_LAUNCH_LEAN(4u, true); else NVO_LAUNCH_LEAN(4u, false); }
+#define NVO_LAUNCH_LEAN_D(HM_, BF_)                                                                                        \
+    do {                                                                                                                   \
+        if (dens_shape) NVO_LAUNCH_LEAN(HM_, BF_, true);                                                                   \
+        else NVO_LAUNCH_LEAN(HM_, BF_, false);                                                                             \
+    } while (0)
+            if (hmask == 6u) { if (out_bf16) NVO_LAUNCH_LEAN_D(6u, true); else NVO_LAUNCH_LEAN_D(6u, false); }
+            else if (hmask == 7u) { if (out_bf16) NVO_LAUNCH_LEAN_D(7u, true); else NVO_LAUNCH_LEAN_D(7u, false); }
+            else { if (out_bf16) NVO_LAUNCH_LEAN_D(4u, true); else NVO_LAUNCH_LEAN_D(4u, false); }
+#undef NVO_LAUNCH_LEAN_D
 #undef NVO_LAUNCH_LEAN
             NVO_CHECK_LAUNCH();
+            if (dens_shape) *density_ran = true;
             return NVO_OK;
         }
         // the plain form (and the shapes the lean form refuses): one workgroup per CU, a whole number of passes each

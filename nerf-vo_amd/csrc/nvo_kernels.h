@@ -158,10 +158,25 @@ int nvo_grid_bwd_stream_launch(const NvoGridLevels& g, NvoGridStream* st, hipStr
 void nvo_grid_slices_destroy(NvoGridSlices* s);
 // dydx_half (optional): [L][3][N] half2, d(out)/d(cell coordinate) for nvo_grid_bwd_input_dydx_launch
 // out_bf16: the encoded features leave as bfloat16 pairs instead of fp16 pairs (bf16 MLP mode)
+// Density epilogue of the small-grid forward (nullable argument of nvo_grid_fwd_launch): the 16-wide, one-hidden-layer
+// ReLU network behind a 5-level grid (the proposal networks) evaluated by the grid kernel itself, on the features it has
+// just rounded -- the bits k_mlp_fwd<16,16,1,16> computes from the stored features, without the second launch.
+struct NvoGridDensity {
+    const void* weights;  // [16][16] first layer | [16][16] output layer; elements fp16, or bf16 with out_bf16
+    void* output;         // [N] column 0 of the output layer (the compact form), same element type
+    void* hidden;         // [N][16] hidden activations, or nullptr (inference; backward that recomputes them)
+    int out_act;          // NVO_ACT_* of the output layer
+    int store_encoded;    // 0: out_half is NOT written (no backward will read the features)
+};
+// density / density_ran: when `density` is given and the launch qualifies for the epilogue (lean small-grid form, N a
+// multiple of 16, no indices / dydx; n_live then bounds BOTH outputs to whole 16-row tiles, as k_mlp_fwd does),
+// *density_ran = true and the network's output is written; otherwise *density_ran = false, the features are stored
+// whatever store_encoded says, and the caller runs the network as a kernel of its own.
 int nvo_grid_fwd_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N, const float* x,
                         const void* table_half, void* out_half, bool soa, uint32_t* indices,
                         void* dydx_half = nullptr, bool out_bf16 = false, const uint32_t* n_live = nullptr,
-                        bool runs = false, int small_form = -1);
+                        bool runs = false, int small_form = -1, const NvoGridDensity* density = nullptr,
+                        bool* density_ran = nullptr);
 // small_form: form of the small-grid forward (5-level grids whose two coarsest levels fit the LDS): -1 = the default
 // (the instruction-lean form), 0 = the generic kernel, 1 plain, 4 instruction-lean + pipelined; anything else is an
 // error.  All forms produce the same bits.

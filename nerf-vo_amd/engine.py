@@ -209,6 +209,9 @@ class EngineConfig:
     # weights, embedding, poses; one small launch) -- optimizer_step.  With a process group the check stays behind the
     # reduction (another rank may have overflowed).
     producer_overflow_flags: bool = True
+    # proposal networks, module option fuse_encoding: 2 = density network as the epilogue of the small-grid forward
+    # (default), 0 = grid kernel + MLP kernel (A/B, tests).  Bit-identical.
+    proposal_fuse_encoding: int = 2
     log_every: int = 10                   # LoggingConfig.steps_per_log of the trainer mirror
     seed: int = 1337
 
@@ -290,8 +293,12 @@ class NerfactoEngine:
         for m in self.prop_nets:
             m.set_option("grid_bwd_dense_share", int(dense_share))
             m.set_option("grid_acc_bits", 32)
-            # (module option fuse_encoding -- the hash grid inside the MLP kernel's operand load -- stays off: measured
-            # 51.5 us per launch against 35 + 8.2 us for the two kernels)
+            # fuse_encoding = 2: the 10 -> 16 -> 1 density network runs as the EPILOGUE of the small-grid forward, on the
+            # features the grid kernel has just rounded (same matrix instructions, same bits) -- no second launch, no
+            # weight staging and feature read-back per level of the sampling prefix.  EXPERIMENTS.md 12.2 has the
+            # measurement.  (Value 1, the hash grid inside the MLP kernel's operand load, lost: 51.5 us per launch
+            # against 35 + 8.2 us for the two kernels.)
+            m.set_option("fuse_encoding", int(cfg.proposal_fuse_encoding))
             # under tcnn's static loss scale most proposal samples carry an exactly zero gradient after a few hundred steps:
             # scan the live ones only (the launch leaves at once while >= 3/4 of the samples are live)
             m.set_option("grid_compact_live", 1)
@@ -669,12 +676,16 @@ class NerfactoEngine:
             runs_mask = int(os.environ.get("NVO_RENDER_RUNS", "7"))  # A/B: bit k = network k walks runs (proposal 0, 1, main)
             for k_, m in enumerate(nets):
                 m.set_option("grid_fwd_runs", (runs_mask >> k_) & 1)
+            for m in self.prop_nets:  # no backward follows: the epilogue form of the forward leaves the feature store out
+                m.set_option("store_encoded", 0)
             try:
                 return self._forward_body(ws, training, anneal, jitters, cam_idx_for_embedding, embedding_ptr, stream,
                                           anneal_dev, skip_head)
             finally:
                 for m in nets:
                     m.set_option("grid_fwd_runs", 0)
+                for m in self.prop_nets:
+                    m.set_option("store_encoded", 1)
         return self._forward_body(ws, training, anneal, jitters, cam_idx_for_embedding, embedding_ptr, stream, anneal_dev,
                                   skip_head)
 
