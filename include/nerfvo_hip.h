@@ -933,6 +933,34 @@ typedef struct nvo_depth_align_args {
 uint64_t nvo_depth_align_scratch_bytes(uint32_t K, uint32_t M);
 int nvo_depth_align(nvo_stream_t stream, const nvo_depth_align_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * H. TSDF fusion of rendered frames into a dense volume (the integration step of the reference's
+ *    integrate_mesh, evaluation/evaluation_utils.py:160-227 there, which runs Open3D's VoxelBlockGrid
+ *    on the CPU).  DESIGN.md "TSDF fusion" states the rule; tests/helpers/tsdf_oracle.py restates it in float64.
+ *    Volume: three caller-owned device tensors, z fastest: tsdf [nx][ny][nz], weight [nx][ny][nz],
+ *    color [3][nx][ny][nz] (planar, 0..255); nx*ny*nz < 2^31.  Voxel (i,j,k) samples lower + (i,j,k) * voxel_size.
+ *    One launch applies K <= NVO_TSDF_MAX_FRAMES frames in table order:
+ *    frames [K][16] = world->camera 3x4 row-major, then fx fy cx cy; depth [K][H][W] metres; rgb [K][H][W][3].
+ *    A voxel's five values stay in registers across the K frames and are written once, if any frame touched them:
+ *    the result does not depend on how a frame sequence is cut into launches.  No atomics, no allocation.
+ * ---------------------------------------------------------------------------------------------- */
+#define NVO_TSDF_MAX_FRAMES 16
+typedef struct nvo_tsdf_args {
+    float* tsdf;
+    float* weight;
+    float* color;
+    const float* frames;
+    const float* depth;
+    const uint8_t* rgb;
+    uint32_t nx, ny, nz;
+    uint32_t K, H, W;
+    float lower_x, lower_y, lower_z;
+    float voxel_size;            /* > 0 */
+    float trunc;                 /* truncation distance in metres, > 0 */
+    float depth_max;             /* depths outside (0, depth_max] are ignored */
+} nvo_tsdf_args;
+int nvo_tsdf_integrate(nvo_stream_t stream, const nvo_tsdf_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,16 @@ class NgpAliveArgs(C.Structure):
                 ("kept_base", _u32), ("t_next", _p), ("resume_out", _p), ("carry_out", _p)]
 
 
+class TsdfArgs(C.Structure):
+    """mirror of nvo_tsdf_args"""
+    _fields_ = [("tsdf", _p), ("weight", _p), ("color", _p), ("frames", _p), ("depth", _p), ("rgb", _p),
+                ("nx", _u32), ("ny", _u32), ("nz", _u32), ("K", _u32), ("H", _u32), ("W", _u32),
+                ("lower_x", _f), ("lower_y", _f), ("lower_z", _f), ("voxel_size", _f), ("trunc", _f), ("depth_max", _f)]
+
+
+TSDF_MAX_FRAMES = 16  # NVO_TSDF_MAX_FRAMES
+
+
 _SIGNATURES = {
     "nvo_last_error": (C.c_char_p, []),
     "nvo_version": (_int, []),
@@ -208,6 +218,8 @@ _SIGNATURES = {
     "nvo_ngp_thickness": (_int, [_p, _u32, _p, _u32, _int, _p]),
     "nvo_ngp_thickness_splat": (_int, [_p, _u32, _p, _u32, _p, _p]),
     "nvo_fill_i32": (_int, [_p, _u32, _p, _i32]),
+    # group H
+    "nvo_tsdf_integrate": (_int, [_p, C.POINTER(TsdfArgs)]),
     # group E
     "nvo_adam_step": (_int, [_p, _u64, _p, _p, _p, _int, _p, _p, _f, _f, _f, _f, _u32, _f, _f, _p, _p]),
     "nvo_write_floats": (_int, [_p, _p, _u32, _p]),

@@ -11,7 +11,8 @@ Mirrors the behaviour of the reference's
 over ``nerf_vo_amd.mapping.renderer.NeRFRenderer`` objects.  Images are written with PIL (JPEG quality 95 is
 OpenCV's ``imwrite`` default; 16-bit PNG depth) because OpenCV is not part of this image.  LPIPS needs
 pretrained AlexNet weights that cannot be fetched here: ``lpips_loss`` is an optional callable and the
-``lpips`` column is omitted without it.  3-D (mesh) metrics are out of scope.
+``lpips`` column is omitted without it.  3-D (mesh) metrics are out of scope; the mesh itself
+is produced: ``EvaluationRenderer.render_mesh`` (TSDF fusion of the rendered frames, tsdf.py).
 
 The numeric functions are pinned by the reference's own outputs: tests/golden/make_golden_evaluation.py executes
 the reference's definitions on seeded inputs and tests/test_evaluation_cpu.py compares.
@@ -208,6 +209,33 @@ class EvaluationRenderer:
             self._render_frame(pose, f"{self.dir_prediction}/{folder}/color/{index:06d}.jpg",
                                f"{self.dir_prediction}/{folder}/depth/{index:06d}.png")
         return indices
+
+    def render_mesh(self, source: str = "frames", mode: str = "evaluation_frames") -> str:
+        """``mesh/mesh_from_<mode>.ply`` fused from the colour / depth files ``render_frames(mode)`` wrote (rendered first
+        when their folder is absent) at the ground-truth poses of those frames (renderer.py:126-164, 265-273): TSDF fusion
+        on the GPU, nerf_vo_amd/tsdf.py.  Returns the file's path."""
+        if source == "nerf":
+            raise NotImplementedError(
+                "render_mesh(source='nerf') (the reference's crop of a density mesh to the ground-truth mesh's bounds) is not "
+                "built; the density mesh itself is: InstantNGPRenderer.render_mesh(file_mesh, resolution, lower_bound, "
+                "upper_bound) / pyngp.Testbed.compute_and_save_marching_cubes_mesh(filename, resolution, aabb)")
+        if source != "frames":
+            raise NotImplementedError(source)
+        from .tsdf import integrate_mesh
+
+        folder, indices = self._process_mode(mode)
+        os.makedirs(f"{self.dir_prediction}/mesh", exist_ok=True)
+        if not os.path.exists(f"{self.dir_prediction}/{folder}"):
+            self.render_frames(mode=mode)
+        file_mesh = f"{self.dir_prediction}/mesh/mesh_from_{mode}.ply"
+        color_dir, depth_dir = f"{self.dir_prediction}/{folder}/color", f"{self.dir_prediction}/{folder}/depth"
+        colors = [read_color(os.path.join(color_dir, f)) for f in sorted(os.listdir(color_dir)) if f.endswith(".jpg")]
+        depths = [read_depth_png16(os.path.join(depth_dir, f)) / self.dataset.camera_intrinsics["depth_scale"]
+                  for f in sorted(os.listdir(depth_dir)) if f.endswith(".png")]
+        extrinsics = np.stack([np.asarray(self.dataset.camera_extrinsics[i], dtype=np.float64) for i in indices])
+        integrate_mesh(file_mesh=file_mesh, camera_intrinsics=self.dataset.camera_intrinsics, camera_extrinsics=extrinsics,
+                       frames_color=colors, frames_depth=depths)
+        return file_mesh
 
     def export_keyframe_poses(self) -> np.ndarray:
         """matrices/matrices_origin2frame_keyframes_mapping.json: training poses with the translation in

@@ -1,6 +1,7 @@
 """Iso-surface extraction for the occupancy-grid back-end's ``compute_and_save_marching_cubes_mesh`` (the call the
 reference makes at /root/reference/evaluation/nerf_renderer.py:296-300; mesh evaluation itself is SURVEY.md section 2
-out of scope).  Off the hot path: plain torch tensor ops on whatever device holds the density samples.
+out of scope) and, with a validity mask, for the TSDF volume of tsdf.py (mesh from rendered frames).  Off the hot path:
+plain torch tensor ops on whatever device holds the samples.
 
 The surface is extracted with MARCHING TETRAHEDRA -- every grid cube is cut into the six tetrahedra around its main
 diagonal and each tetrahedron contributes zero, one or two triangles from its four corner signs -- not with the
@@ -46,9 +47,10 @@ _INSIDE_REF = torch.tensor([next((k for k in range(4) if (case >> k) & 1), -1) i
 
 
 @torch.no_grad()
-def marching_tetrahedra(values: torch.Tensor, lower, upper, threshold: float, slab: int = 16):
+def marching_tetrahedra(values: torch.Tensor, lower, upper, threshold: float, slab: int = 16, valid=None):
     """values [nx, ny, nz] sampled at the corners of a regular grid spanning [lower, upper] -> (vertices [V, 3] float32,
-    faces [F, 3] int64).  Vertices shared by neighbouring triangles are merged."""
+    faces [F, 3] int64).  Vertices shared by neighbouring triangles are merged.  ``valid`` (bool [nx, ny, nz]): a cube
+    contributes only if all eight of its corners are valid (samples nobody observed: the TSDF volume of tsdf.py)."""
     dev = values.device
     nx, ny, nz = values.shape
     lo = torch.as_tensor(lower, dtype=torch.float32, device=dev)
@@ -63,6 +65,10 @@ def marching_tetrahedra(values: torch.Tensor, lower, upper, threshold: float, sl
         # cubes of the slab whose corners are not all on one side
         c = torch.stack([inside[dx:nx - 1 + dx, dy:ny - 1 + dy, dz:z1 - z0 + dz] for dx, dy, dz in corners.tolist()], dim=-1)
         mixed = c.any(dim=-1) & ~c.all(dim=-1)
+        if valid is not None:
+            ok = valid[:, :, z0:z1 + 1]
+            for dx, dy, dz in corners.tolist():
+                mixed &= ok[dx:nx - 1 + dx, dy:ny - 1 + dy, dz:z1 - z0 + dz]
         cube = mixed.nonzero()  # [M, 3] (x, y, z - z0)
         if cube.numel() == 0:
             continue
@@ -74,7 +80,7 @@ def marching_tetrahedra(values: torch.Tensor, lower, upper, threshold: float, sl
         tp = pos[:, tets]  # [M, 6, 4, 3]
         case = ((tv > threshold).long() * torch.tensor([1, 2, 4, 8], device=dev)).sum(-1)  # [M, 6]
         edges = table[case]  # [M, 6, 2, 3, 2]
-        valid = edges[..., 0, 0] >= 0  # [M, 6, 2]
+        has_tri = edges[..., 0, 0] >= 0  # [M, 6, 2]
         e = edges.clamp(min=0)
         M = tv.shape[0]
         idx_m = torch.arange(M, device=dev)[:, None, None, None].expand(M, 6, 2, 3)
@@ -92,36 +98,62 @@ def marching_tetrahedra(values: torch.Tensor, lower, upper, threshold: float, sl
         p1 = torch.where(flip[..., None], pts[..., 2, :], pts[..., 1, :])
         p2 = torch.where(flip[..., None], pts[..., 1, :], pts[..., 2, :])
         pts = torch.stack([pts[..., 0, :], p1, p2], dim=-2)
-        tris.append(pts[valid])
+        tris.append(pts[has_tri])
     if not tris:
         return torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.long, device=dev)
     soup = torch.cat(tris).reshape(-1, 3)  # [3 F, 3] grid coordinates
     # merge shared vertices (cut points lie on grid edges: quantise to 1/4096 of a cell)
     key = torch.round(soup * 4096.0).long()
     uniq, inverse = torch.unique(key, dim=0, return_inverse=True)
-    verts = torch.zeros(uniq.shape[0], 3, device=dev).index_copy_(0, inverse, soup)
+    # the merged vertex takes the position of its LAST occurrence in the soup -- what index_copy_(0, inverse, soup) gives
+    # when it runs sequentially; the copies differ in the last bit, and with several threads (or on a GPU) index_copy_
+    # keeps whichever duplicate was written last, differently from run to run
+    order = torch.arange(soup.shape[0], device=dev)
+    last = torch.zeros(uniq.shape[0], dtype=torch.long, device=dev).scatter_reduce_(0, inverse, order, "amax")
+    verts = soup[last]
     faces = inverse.view(-1, 3)
     faces = faces[(faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])]
     return lo + verts * step, faces
 
 
-def write_mesh(path: str, vertices: torch.Tensor, faces: torch.Tensor) -> None:
-    """.obj (text) or .ply (binary little endian), by extension."""
+def write_mesh(path: str, vertices: torch.Tensor, faces: torch.Tensor, colors=None, normals=None) -> None:
+    """.obj (text) or .ply (binary little endian), by extension.  Per-vertex ``normals`` (float [V, 3]) become ``vn``
+    lines / ``nx ny nz`` properties, per-vertex ``colors`` (uint8 [V, 3]) the ``red green blue`` properties of a .ply
+    (.obj has no standard vertex colour: they are not written there)."""
     v = vertices.detach().cpu().numpy().astype(np.float32)
     f = faces.detach().cpu().numpy().astype(np.int32)
+    vn = None if normals is None else torch.as_tensor(normals).detach().cpu().numpy().astype(np.float32).reshape(-1, 3)
+    vc = None if colors is None else torch.as_tensor(colors).detach().cpu().numpy().astype(np.uint8).reshape(-1, 3)
+    if (vn is not None and vn.shape[0] != v.shape[0]) or (vc is not None and vc.shape[0] != v.shape[0]):
+        raise ValueError("write_mesh: colors / normals must have one row per vertex")
     if path.lower().endswith(".obj"):
         with open(path, "w") as fh:
             fh.write("# nerf_vo_amd marching-tetrahedra mesh\n")
             for p in v:
                 fh.write(f"v {p[0]:.6f} {p[1]:.6f} {p[2]:.6f}\n")
+            if vn is not None:
+                for p in vn:
+                    fh.write(f"vn {p[0]:.6f} {p[1]:.6f} {p[2]:.6f}\n")
             for t in f:
                 fh.write(f"f {t[0] + 1} {t[1] + 1} {t[2] + 1}\n")
         return
     with open(path, "wb") as fh:
         fh.write(("ply\nformat binary_little_endian 1.0\ncomment nerf_vo_amd marching-tetrahedra mesh\n"
                   f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n"
-                  f"element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n").encode())
-        fh.write(v.tobytes())
+                  + ("property float nx\nproperty float ny\nproperty float nz\n" if vn is not None else "")
+                  + ("property uchar red\nproperty uchar green\nproperty uchar blue\n" if vc is not None else "")
+                  + f"element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n").encode())
+        if vn is None and vc is None:
+            fh.write(v.tobytes())
+        else:
+            fields = [("p", "<f4", 3)] + ([("n", "<f4", 3)] if vn is not None else []) + ([("c", "u1", 3)] if vc is not None else [])
+            vert = np.empty(v.shape[0], dtype=np.dtype(fields))
+            vert["p"] = v
+            if vn is not None:
+                vert["n"] = vn
+            if vc is not None:
+                vert["c"] = vc
+            fh.write(vert.tobytes())
         rec = np.empty(f.shape[0], dtype=np.dtype([("n", "u1"), ("i", "<i4", 3)]))
         rec["n"] = 3
         rec["i"] = f

@@ -105,7 +105,7 @@ def _log(mapper):
 
 def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, eval_frames=8, chunk=8, device="cuda:0",
         camera_optimizer_mode=None, pose_noise=None, deterministic=False, seed=42, dynamic_loss_scale=None, out_dir=None,
-        quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None):
+        quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None, mesh=False):
     """``method``: 'nerfstudio' (the default mapper) or 'instant-ngp' (the occupancy-grid back-end through the pyngp facade,
     /root/reference/nerf_vo/mapping/instant_ngp.py + evaluation/nerf_renderer.py:221-320; the room is shrunk by
     ``scene_scale``, default 0.5, so that it lies inside that back-end's scene box: it takes poses as they come)."""
@@ -176,6 +176,12 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
     renderer = EvaluationRenderer(dataset=ds, nerf=nerf, keyframes=kf, dir_prediction=args.dir_prediction)
     renderer.render_frames(mode="evaluation_frames")
     exported = renderer.export_keyframe_poses()
+    mesh_info = None
+    if mesh:  # the protocol's last render step (run.py:71): mesh/mesh_from_evaluation_frames.ply
+        t_mesh = time.perf_counter()
+        file_mesh = renderer.render_mesh(source="frames", mode="evaluation_frames")
+        mesh_info = {"file": file_mesh if not own_dir else os.path.basename(file_mesh), "bytes": os.path.getsize(file_mesh),
+                     "seconds": time.perf_counter() - t_mesh}
     ev = Evaluator2D(ds, kf, args.dir_prediction, out_dir + "/results")
     m_eval = ev.calculate_metrics_2d(mode="evaluation_frames")
     m_kf = {}
@@ -206,6 +212,8 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
            "pose_error_gauge_split": _gauge_split(traj, gt_kf),
            "pose_adjustment_rms": float((eng.pose_adjustment if ngp else eng.view("camera_opt.pose_adjustment")).pow(2).mean().sqrt()),
            "deterministic": bool(deterministic), "seed": seed, "exported_poses": int(exported.shape[0])}
+    if mesh_info is not None:
+        res["mesh"] = mesh_info
     if ngp:
         res.update({"camera_optimizer_mode": "instant-ngp extrinsics", "ms_per_step_incl_ingest": 1e3 * train_s / iterations,
                     "rays_per_batch": eng.rays_per_batch, "applied_steps": eng.applied_steps})
@@ -234,8 +242,9 @@ if __name__ == "__main__":
     ap.add_argument("--no-keyframe-views", action="store_true")
     ap.add_argument("--method", default="nerfstudio", choices=["nerfstudio", "instant-ngp"])
     ap.add_argument("--scene-scale", type=float, default=None)
+    ap.add_argument("--mesh", action="store_true", help="also fuse the rendered evaluation frames into mesh/mesh_from_evaluation_frames.ply")
     a = ap.parse_args()
     run(a.keyframes, a.height, a.width, a.iterations, eval_frames=a.eval_frames, camera_optimizer_mode=a.camera_optimizer_mode,
         pose_noise=a.pose_noise, deterministic=a.deterministic, seed=a.seed, quiet=False,
         dynamic_loss_scale=False if a.static_loss_scale else None, keyframe_views=not a.no_keyframe_views,
-        method=a.method, scene_scale=a.scene_scale)
+        method=a.method, scene_scale=a.scene_scale, mesh=a.mesh)
