@@ -961,6 +961,40 @@ typedef struct nvo_tsdf_args {
 } nvo_tsdf_args;
 int nvo_tsdf_integrate(nvo_stream_t stream, const nvo_tsdf_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * I. Exact nearest-neighbour query of N points against M target points binned into a uniform cell grid: the search
+ *    behind the 3-D mesh metrics and their ICP alignment (the reference's calculate_metrics_3d,
+ *    evaluation/evaluation_utils.py:447-512 there, which runs scipy's cKDTree and Open3D's ICP on the CPU).
+ *    DESIGN.md "Nearest-neighbour search" states the rule; tests/helpers/nn_oracle.py restates it by brute force.
+ *    Grid: cell (ix,iy,iz) covers lower + (ix,iy,iz) * cell_size .. + cell_size and has the linear id (iz*gy + iy)*gx + ix
+ *    (x fastest); gx, gy, gz in 1..NVO_NN_MAX_CELLS_PER_AXIS.  points [M][3] are sorted by cell id, points of cell c are
+ *    rows cell_start[c] .. cell_start[c+1]-1, point_index [M] is each row's index before the sort.  Every target point
+ *    lies in the grid's box and its cell is floor((p - lower) / cell_size) per axis, clamped to the grid, up to the
+ *    rounding of that expression in fp32.
+ *    out_dist2[i] = min over ALL M points of (dx*dx + dy*dy) + dz*dz in fp32, d = query - point; out_index[i] = the smallest
+ *    original index attaining it.  With a finite max_dist only points with dist2 <= max_dist*max_dist (fp32 product)
+ *    count, and a query without one gets +inf and -1.  With has_xf the query is first mapped to
+ *    x' = ((xf[0]*x + xf[1]*y) + xf[2]*z) + xf[3] (rows 1, 2 likewise) in fp32.  The result is that of the brute-force
+ *    evaluation bit for bit, whatever the cell size, the grid dimensions and the launch shape.  No atomics, no allocation.
+ * ---------------------------------------------------------------------------------------------- */
+#define NVO_NN_MAX_CELLS_PER_AXIS 1024
+typedef struct nvo_nn_args {
+    const float* points;         /* [M][3], sorted by cell */
+    const uint32_t* point_index; /* [M] */
+    const uint32_t* cell_start;  /* [gx*gy*gz + 1] */
+    const float* queries;        /* [N][3] */
+    float* out_dist2;            /* [N] */
+    int32_t* out_index;          /* [N] */
+    uint32_t N, M;               /* 1 .. 2^31 - 1 each */
+    uint32_t gx, gy, gz;
+    float lower_x, lower_y, lower_z;
+    float cell_size;             /* > 0, finite */
+    float max_dist;              /* > 0; INFINITY = unbounded */
+    int32_t has_xf;
+    float xf[12];                /* row-major 3x4 rigid transform of the queries, read when has_xf != 0 */
+} nvo_nn_args;
+int nvo_nn_query(nvo_stream_t stream, const nvo_nn_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,17 @@ class TsdfArgs(C.Structure):
 TSDF_MAX_FRAMES = 16  # NVO_TSDF_MAX_FRAMES
 
 
+class NnArgs(C.Structure):
+    """mirror of nvo_nn_args"""
+    _fields_ = [("points", _p), ("point_index", _p), ("cell_start", _p), ("queries", _p), ("out_dist2", _p), ("out_index", _p),
+                ("N", _u32), ("M", _u32), ("gx", _u32), ("gy", _u32), ("gz", _u32),
+                ("lower_x", _f), ("lower_y", _f), ("lower_z", _f), ("cell_size", _f), ("max_dist", _f),
+                ("has_xf", _i32), ("xf", _f * 12)]
+
+
+NN_MAX_CELLS_PER_AXIS = 1024  # NVO_NN_MAX_CELLS_PER_AXIS
+
+
 _SIGNATURES = {
     "nvo_last_error": (C.c_char_p, []),
     "nvo_version": (_int, []),
@@ -220,6 +231,8 @@ _SIGNATURES = {
     "nvo_fill_i32": (_int, [_p, _u32, _p, _i32]),
     # group H
     "nvo_tsdf_integrate": (_int, [_p, C.POINTER(TsdfArgs)]),
+    # group I
+    "nvo_nn_query": (_int, [_p, C.POINTER(NnArgs)]),
     # group E
     "nvo_adam_step": (_int, [_p, _u64, _p, _p, _p, _int, _p, _p, _f, _f, _f, _f, _u32, _f, _f, _p, _p]),
     "nvo_write_floats": (_int, [_p, _p, _u32, _p]),

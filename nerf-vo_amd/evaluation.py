@@ -11,11 +11,20 @@ Mirrors the behaviour of the reference's
 over ``nerf_vo_amd.mapping.renderer.NeRFRenderer`` objects.  Images are written with PIL (JPEG quality 95 is
 OpenCV's ``imwrite`` default; 16-bit PNG depth) because OpenCV is not part of this image.  LPIPS needs
 pretrained AlexNet weights that cannot be fetched here: ``lpips_loss`` is an optional callable and the
-``lpips`` column is omitted without it.  3-D (mesh) metrics are out of scope; the mesh itself
-is produced: ``EvaluationRenderer.render_mesh`` (TSDF fusion of the rendered frames, tsdf.py).
+``lpips`` column is omitted without it.
 
-The numeric functions are pinned by the reference's own outputs: tests/golden/make_golden_evaluation.py executes
-the reference's definitions on seeded inputs and tests/test_evaluation_cpu.py compares.
+3-D (mesh) metrics: ``EvaluationRenderer.render_mesh`` produces the mesh (TSDF fusion of the rendered frames, tsdf.py) and
+``calculate_metrics_3d`` / ``Evaluator3D`` score it against the ground-truth mesh the way the reference's
+``calculate_metrics_3d`` (evaluation_utils.py:447-512) and ``Evaluator.calculate_metrics_3d`` (evaluator.py:148-174) do:
+200 000 surface samples per mesh, voxel down-sampling at 1/64, point-to-point ICP of the prediction onto the ground
+truth, nearest-neighbour distances both ways, ``accuracy / completion / precision / recall / f1score`` at 0.05.  The
+reference uses Open3D and scipy on the CPU; here pointcloud.py does the cloud operations and the nearest-neighbour search
+is a HIP kernel (csrc/nn.hip).
+
+The numeric functions are pinned by the reference's own outputs: tests/golden/make_golden_evaluation.py and
+make_golden_metrics3d.py execute the reference's definitions on seeded inputs and tests/test_evaluation_cpu.py /
+test_metrics3d_cpu.py compare.  For the 3-D table that covers the five formulae and the nearest-neighbour distances;
+parity of the sampling, the down-sampling and the ICP with Open3D is UNPINNED (pointcloud.py).
 """
 from __future__ import annotations
 
@@ -282,3 +291,97 @@ class Evaluator2D:
         with open(f"{self.dir_result}/metrics_2d_{folder}.json", "w") as file:
             json.dump(means, file)
         return means
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 3-D (mesh) metrics
+# ---------------------------------------------------------------------------------------------------------------
+METRIC_THRESHOLD_3D = 0.05     # the reference's constants (calculate_metrics_3d)
+NUM_SAMPLE_POINTS_3D = 200000
+VOXEL_SIZE_3D = 1.0 / 64.0
+METRICS_3D = ("accuracy", "completion", "precision", "recall", "f1score")
+
+
+def metrics_3d_from_distances(distances_gt_to_pred, distances_pred_to_gt) -> dict:
+    """The tail of the reference's ``calculate_metrics_3d`` (evaluation_utils.py:496-510), with its names:
+    ``distances_gt_to_pred`` holds, for every PREDICTED point, the distance to its nearest ground-truth point (the query
+    of the ground truth's tree), ``distances_pred_to_gt`` the reverse.  So "accuracy" is prediction -> ground truth and
+    "completion" ground truth -> prediction; precision / recall are the shares below 0.05 (strictly)."""
+    d_gt_to_pred = np.asarray(distances_gt_to_pred, dtype=np.float64)
+    d_pred_to_gt = np.asarray(distances_pred_to_gt, dtype=np.float64)
+    precision = np.mean((d_gt_to_pred < METRIC_THRESHOLD_3D).astype(float))
+    recall = np.mean((d_pred_to_gt < METRIC_THRESHOLD_3D).astype(float))
+    return {"accuracy": float(np.mean(d_gt_to_pred)), "completion": float(np.mean(d_pred_to_gt)),
+            "precision": float(precision), "recall": float(recall),
+            "f1score": float(2 * precision * recall / (precision + recall))}
+
+
+def sample_metric_clouds(mesh_gt, mesh_pred, seed: int = 0, device="cuda", number_of_points: int = NUM_SAMPLE_POINTS_3D,
+                         voxel_size: float = VOXEL_SIZE_3D) -> tuple:
+    """The two clouds the metrics are computed from: ``number_of_points`` uniform surface samples of each mesh (one CPU
+    generator seeded with ``seed``: ground truth first), voxel down-sampled.  float32 [K, 3] tensors on ``device``."""
+    from .pointcloud import sample_points_uniformly, voxel_down_sample
+
+    gen = torch.Generator().manual_seed(int(seed))
+    clouds = []
+    for vertices, faces in (mesh_gt, mesh_pred):
+        v = torch.as_tensor(vertices).to(device)
+        pts = sample_points_uniformly(v, torch.as_tensor(faces).to(device), number_of_points, generator=gen)
+        clouds.append(voxel_down_sample(pts, voxel_size))
+    return clouds[0], clouds[1]
+
+
+def metrics_3d_from_clouds(points_gt: torch.Tensor, points_pred: torch.Tensor, cell_size=None) -> dict:
+    """ICP of the predicted cloud onto the ground-truth cloud (the reference's settings), then the two nearest-neighbour
+    tables and ``metrics_3d_from_distances``.  Both clouds on the GPU."""
+    from .pointcloud import DEFAULT_CELL_SIZE, NeighbourGrid, icp_point_to_point
+
+    cell_size = DEFAULT_CELL_SIZE if cell_size is None else cell_size
+    grid_gt = NeighbourGrid(points_gt, cell_size)
+    transformation, _, _, _ = icp_point_to_point(points_pred, grid_gt)
+    t = torch.from_numpy(transformation).to(points_pred.device)
+    moved = (points_pred.double() @ t[:3, :3].T + t[:3, 3]).float()
+    d2_pred_to_gt, _ = NeighbourGrid(moved, cell_size).query(points_gt)   # for every ground-truth point
+    d2_gt_to_pred, _ = grid_gt.query(moved)                               # for every predicted point
+    return metrics_3d_from_distances(d2_gt_to_pred.double().sqrt().cpu().numpy(), d2_pred_to_gt.double().sqrt().cpu().numpy())
+
+
+def calculate_metrics_3d(mesh_gt, mesh_pred, seed: int = 0, device="cuda") -> dict:
+    """The reference's ``calculate_metrics_3d(mesh_gt, mesh_pred)`` (evaluation_utils.py:466-512); each mesh is a
+    ``(vertices [V, 3], faces [F, 3])`` pair.  ``seed`` fixes the surface samples (Open3D draws them from its global
+    generator)."""
+    points_gt, points_pred = sample_metric_clouds(mesh_gt, mesh_pred, seed=seed, device=device)
+    return metrics_3d_from_clouds(points_gt, points_pred)
+
+
+class Evaluator3D:
+    """``Evaluator.calculate_metrics_3d`` (evaluator.py:148-174): every ``<dir_prediction>/mesh/*.ply`` except
+    ``mesh_from_nerf_raw`` against ``dataset.mesh()`` -> ``<dir_result>/metrics_3d.csv`` (the five metrics and ``mesh``,
+    one row per file, files in sorted order)."""
+
+    def __init__(self, dataset, dir_prediction: str, dir_result: str, seed: int = 0, device="cuda") -> None:
+        self.dataset = dataset
+        self.dir_prediction = dir_prediction
+        self.dir_result = dir_result
+        self.seed = seed
+        self.device = device
+
+    def calculate_metrics_3d(self) -> dict:
+        import pandas as pd
+
+        from .meshing import read_mesh
+
+        mesh_gt, _ = self.dataset.mesh()
+        rows = []
+        for name in sorted(os.listdir(f"{self.dir_prediction}/mesh")):
+            stem, ext = os.path.splitext(name)
+            if ext != ".ply" or stem == "mesh_from_nerf_raw":
+                continue
+            vertices, faces = read_mesh(f"{self.dir_prediction}/mesh/{name}")[:2]
+            row = calculate_metrics_3d(mesh_gt=mesh_gt[:2], mesh_pred=(vertices, faces), seed=self.seed, device=self.device)
+            row["mesh"] = stem
+            rows.append(row)
+        table = pd.DataFrame(rows, columns=list(METRICS_3D) + ["mesh"])
+        os.makedirs(self.dir_result, exist_ok=True)
+        table.to_csv(f"{self.dir_result}/metrics_3d.csv", index=False)
+        return table[list(METRICS_3D)].squeeze().to_dict()

@@ -158,3 +158,68 @@ def write_mesh(path: str, vertices: torch.Tensor, faces: torch.Tensor, colors=No
         rec["n"] = 3
         rec["i"] = f
         fh.write(rec.tobytes())
+
+
+_PLY_TYPES = {"float": "<f4", "float32": "<f4", "uchar": "u1", "uint8": "u1"}
+
+
+def read_mesh(path: str):
+    """A binary-little-endian .ply as ``write_mesh`` writes it -> ``(vertices float32 [V, 3], faces int64 [F, 3], colors
+    uint8 [V, 3] or None, normals float32 [V, 3] or None)`` (CPU tensors).  Vertex properties: ``x y z``, optionally
+    ``nx ny nz`` and ``red green blue``, float / uchar; faces: ``property list uchar int vertex_indices``, triangles only.
+    Anything else (ascii or big-endian files, other elements or properties, polygons) raises ValueError."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"read_mesh: {path} is not a .ply file (no 'ply' ... 'end_header' header)")
+    lines = [ln.strip() for ln in data[:end].decode("ascii", errors="replace").splitlines()]
+    body = memoryview(data)[end + len(b"end_header\n"):]
+    elements, fmt = [], None
+    for ln in lines[1:]:
+        tok = ln.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1:]
+        elif tok[0] == "element" and len(tok) == 3:
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property" and elements:
+            elements[-1][2].append(tok[1:])
+        else:
+            raise ValueError(f"read_mesh: {path}: header line '{ln}' not understood")
+    if fmt != ["binary_little_endian", "1.0"]:
+        raise ValueError(f"read_mesh: {path}: format {' '.join(fmt or ['?'])} -- only binary_little_endian 1.0 (what write_mesh writes) is read")
+    if [e[0] for e in elements] != ["vertex", "face"]:
+        raise ValueError(f"read_mesh: {path}: elements {[e[0] for e in elements]} -- exactly 'vertex' then 'face' expected")
+    (_, n_vert, vprops), (_, n_face, fprops) = elements
+    names = [p[-1] for p in vprops]
+    allowed = {("x", "y", "z"): "float", ("nx", "ny", "nz"): "float", ("red", "green", "blue"): "uchar"}
+    groups = [tuple(names[i:i + 3]) for i in range(0, len(names), 3)]
+    if len(names) % 3 or groups[:1] != [("x", "y", "z")] or any(g not in allowed for g in groups) or len(set(groups)) != len(groups):
+        raise ValueError(f"read_mesh: {path}: vertex properties {names} -- x y z [nx ny nz] [red green blue] expected")
+    fields = []
+    for p, g in zip(vprops, [g for g in groups for _ in range(3)]):
+        if len(p) != 2 or p[0] not in _PLY_TYPES or _PLY_TYPES[p[0]] != _PLY_TYPES[allowed[g]]:
+            raise ValueError(f"read_mesh: {path}: property '{' '.join(p)}' -- {allowed[g]} expected")
+        fields.append((p[1], _PLY_TYPES[p[0]]))
+    if len(fprops) != 1 or fprops[0][:3] not in (["list", "uchar", "int"], ["list", "uint8", "int32"], ["list", "uchar", "int32"],
+                                                 ["list", "uint8", "int"]) or fprops[0][3:] not in (["vertex_indices"], ["vertex_index"]):
+        raise ValueError(f"read_mesh: {path}: face properties {fprops} -- 'list uchar int vertex_indices' expected")
+    vdt = np.dtype(fields)
+    fdt = np.dtype([("n", "u1"), ("i", "<i4", 3)])
+    if len(body) != n_vert * vdt.itemsize + n_face * fdt.itemsize:
+        raise ValueError(f"read_mesh: {path}: {len(body)} bytes of data, {n_vert} vertices and {n_face} triangles need "
+                         f"{n_vert * vdt.itemsize + n_face * fdt.itemsize} (truncated file, or faces that are not triangles)")
+    vert = np.frombuffer(body, dtype=vdt, count=n_vert)
+    face = np.frombuffer(body, dtype=fdt, count=n_face, offset=n_vert * vdt.itemsize)
+    if n_face and not (face["n"] == 3).all():
+        raise ValueError(f"read_mesh: {path}: faces that are not triangles")
+    if n_face and n_vert and (face["i"].min() < 0 or face["i"].max() >= n_vert):
+        raise ValueError(f"read_mesh: {path}: a face index outside 0..{n_vert - 1}")
+
+    def take(g, dt):
+        return torch.from_numpy(np.stack([vert[k] for k in g], axis=1).astype(dt)) if g in groups else None
+
+    return (take(("x", "y", "z"), np.float32), torch.from_numpy(face["i"].astype(np.int64)).reshape(-1, 3),
+            take(("red", "green", "blue"), np.uint8), take(("nx", "ny", "nz"), np.float32))

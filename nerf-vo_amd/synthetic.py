@@ -105,8 +105,9 @@ class SyntheticEvaluationDataset:
     (every frame that is not a keyframe stride), and ``frames_color`` / ``frames_depth`` per mode."""
 
     def __init__(self, num_frames: int = 96, height: int = 120, width: int = 160, evaluation_stride: int = 5,
-                 depth_scale: float = 6553.5, device="cpu", scene_scale: float = 1.0):
+                 depth_scale: float = 6553.5, device="cpu", scene_scale: float = 1.0, dir_dataset: str = None):
         self.device = torch.device(device)  # where the ground-truth frames are ray-cast (values are the same)
+        self.dir_dataset = dir_dataset  # only mesh() needs it: the fused ground-truth mesh is written next to it
         fx, fy, cx, cy = replica_intrinsics(height, width)
         self.camera_intrinsics = {"fx": fx, "fy": fy, "cx": cx, "cy": cy, "height": height, "width": width,
                                   "depth_scale": depth_scale}
@@ -139,3 +140,24 @@ class SyntheticEvaluationDataset:
 
     def frames_depth(self, mode: str = "evaluation_frames", keyframes=None) -> list:
         return [self.render(self.camera_extrinsics[i])[1] for i in self._indices(mode, keyframes)]
+
+    def mesh(self) -> tuple:
+        """``(mesh, path)`` of the ground-truth mesh the 3-D metrics compare against: like the reference's dataset
+        (evaluation/datasets/base_dataset.py:101-111) it is not loaded but fused from ALL ground-truth colour and depth
+        frames with ``tsdf.integrate_mesh`` into ``<dir_dataset>_mesh_fused.ply``, once.  ``mesh`` is what
+        ``meshing.read_mesh`` returns (vertices, faces, colors, normals)."""
+        import os
+
+        from .meshing import read_mesh
+        from .tsdf import integrate_mesh
+
+        if not self.dir_dataset:
+            raise ValueError("SyntheticEvaluationDataset.mesh: construct the dataset with dir_dataset=<scene directory> -- the "
+                             "fused mesh is written to <dir_dataset>_mesh_fused.ply")
+        dir_dataset = os.path.abspath(self.dir_dataset)
+        file_mesh = os.path.dirname(dir_dataset) + f"/{os.path.basename(dir_dataset)}_mesh_fused.ply"
+        if not os.path.exists(file_mesh):
+            os.makedirs(os.path.dirname(file_mesh), exist_ok=True)
+            integrate_mesh(file_mesh=file_mesh, camera_intrinsics=self.camera_intrinsics, camera_extrinsics=self.camera_extrinsics,
+                           frames_color=self.frames_color(mode="all"), frames_depth=self.frames_depth(mode="all"))
+        return read_mesh(file_mesh), file_mesh

@@ -105,12 +105,12 @@ def _log(mapper):
 
 def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, eval_frames=8, chunk=8, device="cuda:0",
         camera_optimizer_mode=None, pose_noise=None, deterministic=False, seed=42, dynamic_loss_scale=None, out_dir=None,
-        quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None, mesh=False):
+        quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None, mesh=False, metrics_3d=False):
     """``method``: 'nerfstudio' (the default mapper) or 'instant-ngp' (the occupancy-grid back-end through the pyngp facade,
     /root/reference/nerf_vo/mapping/instant_ngp.py + evaluation/nerf_renderer.py:221-320; the room is shrunk by
     ``scene_scale``, default 0.5, so that it lies inside that back-end's scene box: it takes poses as they come)."""
     entry.build()
-    from nerf_vo_amd.evaluation import (EvaluationRenderer, Evaluator2D, read_color, transform_matrices_pred2gt)
+    from nerf_vo_amd.evaluation import (EvaluationRenderer, Evaluator2D, Evaluator3D, read_color, transform_matrices_pred2gt)
     from nerf_vo_amd.mapping.dataset import opencv_to_opengl
     from nerf_vo_amd.mapping.nerfstudio_mapper import Nerfstudio
     from nerf_vo_amd.mapping.renderer import NerfstudioRenderer, calculate_psnr_float
@@ -127,7 +127,9 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
         # pixels only at its own aspect -- 160 x 120 renders with fx != fy come out at 13 dB)
         raise SystemExit("--method instant-ngp needs Replica's aspect ratio (e.g. --width 240 --height 136)")
     ds = SyntheticEvaluationDataset(num_frames=n_frames, height=height, width=width, device=dev,
-                                    scene_scale=float(scene_scale) if scene_scale else (0.5 if ngp else 1.0))
+                                    scene_scale=float(scene_scale) if scene_scale else (0.5 if ngp else 1.0),
+                                    dir_dataset=out_dir + "/dataset/synthetic_room")
+    mesh = mesh or metrics_3d  # the 3-D table is computed from the mesh
     kf = list(range(0, n_frames, frame_stride))
     held_out = [i for i in range(n_frames) if i % frame_stride != 0]
     ds.evaluation_frames = [held_out[int(j * len(held_out) / eval_frames)] for j in range(eval_frames)]
@@ -182,6 +184,11 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
         file_mesh = renderer.render_mesh(source="frames", mode="evaluation_frames")
         mesh_info = {"file": file_mesh if not own_dir else os.path.basename(file_mesh), "bytes": os.path.getsize(file_mesh),
                      "seconds": time.perf_counter() - t_mesh}
+    m_3d = None
+    if metrics_3d:  # run.py:79: ground-truth mesh fused from all ground-truth frames, results/metrics_3d.csv
+        t_3d = time.perf_counter()
+        m_3d = Evaluator3D(ds, args.dir_prediction, out_dir + "/results").calculate_metrics_3d()
+        m_3d = {**{k: float(v) for k, v in m_3d.items()}, "seconds_incl_ground_truth_mesh": time.perf_counter() - t_3d}
     ev = Evaluator2D(ds, kf, args.dir_prediction, out_dir + "/results")
     m_eval = ev.calculate_metrics_2d(mode="evaluation_frames")
     m_kf = {}
@@ -214,6 +221,8 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
            "deterministic": bool(deterministic), "seed": seed, "exported_poses": int(exported.shape[0])}
     if mesh_info is not None:
         res["mesh"] = mesh_info
+    if m_3d is not None:
+        res["metrics_3d"] = m_3d
     if ngp:
         res.update({"camera_optimizer_mode": "instant-ngp extrinsics", "ms_per_step_incl_ingest": 1e3 * train_s / iterations,
                     "rays_per_batch": eng.rays_per_batch, "applied_steps": eng.applied_steps})
@@ -243,8 +252,10 @@ if __name__ == "__main__":
     ap.add_argument("--method", default="nerfstudio", choices=["nerfstudio", "instant-ngp"])
     ap.add_argument("--scene-scale", type=float, default=None)
     ap.add_argument("--mesh", action="store_true", help="also fuse the rendered evaluation frames into mesh/mesh_from_evaluation_frames.ply")
+    ap.add_argument("--metrics-3d", action="store_true", help="also score the mesh against the fused ground-truth mesh "
+                    "(results/metrics_3d.csv); implies --mesh")
     a = ap.parse_args()
     run(a.keyframes, a.height, a.width, a.iterations, eval_frames=a.eval_frames, camera_optimizer_mode=a.camera_optimizer_mode,
         pose_noise=a.pose_noise, deterministic=a.deterministic, seed=a.seed, quiet=False,
         dynamic_loss_scale=False if a.static_loss_scale else None, keyframe_views=not a.no_keyframe_views,
-        method=a.method, scene_scale=a.scene_scale, mesh=a.mesh)
+        method=a.method, scene_scale=a.scene_scale, mesh=a.mesh, metrics_3d=a.metrics_3d)
