@@ -159,7 +159,7 @@ int nvo_bwd(nvo_module_t m, nvo_stream_t stream, uint32_t batch, const float* in
 /* Optimiser step inside the parameter backward.  The tile-local record pass of a hash grid (grid_bwd_mode 3, 32-bit
  * accumulators) holds the finished gradient of every entry of its streamed hashed levels in LDS when it flushes: with
  * nvo_set_fused_adam it applies torch.optim.Adam to those entries right there (same arithmetic as
- * nvo_adam_step_groups_scaled, bit for bit) instead of storing the gradient -- 8 bytes of HBM traffic per parameter less
+ * nvo_adam_step, bit for bit) instead of storing the gradient -- 8 bytes of HBM traffic per parameter less
  * (gradient write + the optimiser's read), and the optimiser launch shrinks to the parameters outside
  * [first_param, first_param + n_params) (nvo_fused_adam_range, relative to the module's first parameter).
  * Preconditions the caller guarantees: the group's overflow flag word is FINAL when the backward of this module runs
@@ -169,7 +169,7 @@ int nvo_bwd(nvo_module_t m, nvo_stream_t stream, uint32_t batch, const float* in
  * set, record / run the backward, then switch off (args = NULL) for launches that want the gradient.
  * The fused step applies NO weight decay (there is no such field): both engines decay MLP weights only, never a hash
  * table (instant-ngp's l2_reg, nvo_adam_group::weight_decay); a caller whose optimiser decays the grid range must keep
- * that range in its own nvo_adam_step_groups launch.  While a step is armed the slice-owner items of the coarse levels
+ * that range in its own nvo_adam_step launch.  While a step is armed the slice-owner items of the coarse levels
  * run IN stream order in front of the accumulate pass (option grid_stream_overlap is ignored): they may raise the flag. */
 typedef struct nvo_fused_adam_args {
     float* params;                 /* fp32 master weights: pointer to THIS MODULE's first parameter */
@@ -183,9 +183,9 @@ typedef struct nvo_fused_adam_args {
     float lr, grad_scale, beta1, beta2, eps;
     uint32_t step;                 /* bias_dev == NULL: bias corrections of step `step` (counted from 1), computed on the host
                                       exactly as nvo_adam_step does */
-    /* optional: tcnn EmaOptimizer folded in (nvo_ema_update_dev on the same entries, same arithmetic): the stepped
+    /* optional: tcnn EmaOptimizer folded in (nvo_ema_update on the same entries, same arithmetic): the stepped
      * weights are averaged into ema / ema_half right away.  ema_step_dev is only READ (the caller's
-     * nvo_ema_update_dev launch over the rest of the parameters advances it). */
+     * nvo_ema_update launch over the rest of the parameters advances it). */
     float* ema;                    /* fp32 average, same origin as params; NULL = no averaging */
     void* ema_half;                /* fp16 copy of the average (nullable) */
     float ema_decay;
@@ -727,135 +727,68 @@ int nvo_ngp_thickness_splat(nvo_stream_t stream, uint32_t n, const void* density
 int nvo_fill_i32(nvo_stream_t stream, uint32_t n, int32_t* ptr, int32_t value);
 
 /* ------------------------------------------------------------------------------------------------
- * E. Optimiser (torch.optim.Adam as configured at /root/reference/nerf_vo/mapping/nerfstudio.py:84-100
- *    + GradScaler's skip-on-non-finite from mixed_precision=True, nerfstudio.py:59).
+ * E. Optimiser: torch.optim.Adam (no AMSGrad, L2 weight decay folded into the gradient) under torch's GradScaler --
+ *    a parameter group whose gradients hold a non-finite value is skipped, its step counter does not advance, and
+ *    the loss scale backs off -- plus instant-ngp's weight average.  Four jobs, one entry point each: the step
+ *    (nvo_adam_step), the non-finite scan (nvo_nonfinite_flag), the commit (nvo_opt_commit) and the average
+ *    (nvo_ema_update); the casts and small helpers follow.
+ *    Everywhere a `grads_fmt` / `wire_fmt` argument appears, 0 = fp32, 1 = fp16, 2 = bfloat16 (the 2-byte forms are
+ *    the buffer a compressed gradient exchange leaves behind: no cast-back pass).
  * ---------------------------------------------------------------------------------------------- */
-/* One fused pass over params[n]: updates exp_avg / exp_avg_sq / params and, if params_half != NULL,
- * the fp16 working copy.  grads are multiplied by grad_scale first (1/loss_scale).  step counts from 1.
- * skip_flag: device uint32 or NULL; a non-zero value makes the call a no-op. */
-int nvo_adam_step(nvo_stream_t stream, uint64_t n, float* params, void* params_half,
-                  const void* grads, int grads_are_half, float* exp_avg, float* exp_avg_sq, float lr,
-                  float beta1, float beta2, float eps, uint32_t step, float grad_scale, float weight_decay,
-                  const uint32_t* skip_flag, const float* hyper_dev);
-/* The same update for up to 4 parameter groups of ONE flat buffer in one launch (the optimisers of
- * /root/reference/nerf_vo/mapping/nerfstudio.py:84-100 differ only in learning rate and step count).
- * offset / n are in elements of the flat buffers; hyper_dev: optional device float[3] = {lr, 1 - beta1^t,
- * sqrt(1 - beta2^t)} that overrides lr / step (graph replay). */
+/* One parameter group of a step: elements [offset, offset + n) of the flat buffers. */
 typedef struct nvo_adam_group {
     uint64_t offset, n;
     float lr;
-    uint32_t step;
+    uint32_t step;            /* counts from 1; ignored when bias_dev != NULL */
+    /* hyper_dev (nullable): device float[3] = {lr, 1 - beta1^t, sqrt(1 - beta2^t)} overriding lr / step, so that a
+     * captured hipGraph of the step can be replayed with new values. */
     const float* hyper_dev;
     /* bias_dev (nullable): device float[2] = {1 - beta1^t, sqrt(1 - beta2^t)} of the group's NEXT applied step, kept
      * by nvo_opt_commit next to its applied-step counter (`step` and hyper_dev[1..2] are then ignored): the counter
      * advances iff the group was not skipped -- torch.optim.Adam's state['step'] under GradScaler.step, which does not
      * count skipped steps. */
     const float* bias_dev;
-    /* which word of skip_flags belongs to this group: the group's index in `groups` unless flag_slot_set != 0 (a step
-     * that runs its groups in two launches keeps ONE flag word per group that way) */
+    /* which word of nvo_adam_args::skip_flags belongs to this group (< 4): several groups may share one, and a step
+     * that runs its groups in two launches keeps ONE flag word per group */
     uint32_t flag_slot;
-    uint32_t flag_slot_set;
-    /* L2 weight decay of this group (folded into the gradient); used instead of the call's weight_decay when
-     * weight_decay_set != 0 -- instant-ngp decays its MLP weights and leaves the hash table alone, in one launch */
+    /* L2 weight decay of this group (folded into the gradient) -- instant-ngp decays its MLP weights and leaves the
+     * hash table alone, in one launch */
     float weight_decay;
-    uint32_t weight_decay_set;
 } nvo_adam_group;
-int nvo_adam_step_groups(nvo_stream_t stream, uint32_t n_groups, const nvo_adam_group* groups, float* params,
-                         void* params_half, const void* grads, int grads_are_half, float* exp_avg, float* exp_avg_sq,
-                         float beta1, float beta2, float eps, float grad_scale, float weight_decay,
-                         const uint32_t* skip_flags);
-/* skip_flags: device uint32 [n_groups] or NULL; group i is a no-op when skip_flags[i] != 0 -- GradScaler.step
- * decides per optimiser (nerfstudio's optimizer_scaler_step_all calls it once per parameter group).
- *
- * nvo_nonfinite_flag over up to 4 ranges (element offsets / sizes, host arrays) of one gradient buffer in one
- * launch: flags[i] (device uint32 [n_ranges], reset first) is raised iff range i holds an inf / NaN. */
-int nvo_nonfinite_flag_ranges(nvo_stream_t stream, uint32_t n_ranges, const uint64_t* offsets, const uint64_t* sizes,
-                              const void* grads, int grads_are_half, uint32_t* flags);
-/* The same without resetting the flag words first (they were cleared earlier, e.g. by the step's nvo_zero_ranges):
- * one launch less in front of the optimiser. */
-/* The same over up to 8 spans with an EXPLICIT flag word each (flags[slots[i]] |= 1; several spans may share a word):
- * the step whose overflow flags are raised at the source scans the small non-grid ranges of its groups -- fused-MLP
- * weight gradients, embedding, poses -- where every 16-bit overflow INSIDE the backward chain ends up (dW = dZ x H of
- * the layer that overflowed), see EngineConfig.producer_overflow_flags. */
-int nvo_nonfinite_flag_spans_or(nvo_stream_t stream, uint32_t n_spans, const uint64_t* offsets, const uint64_t* sizes,
-                                const uint32_t* slots, const void* grads, int grads_are_half, uint32_t* flags);
-int nvo_nonfinite_flag_ranges_or(nvo_stream_t stream, uint32_t n_ranges, const uint64_t* offsets, const uint64_t* sizes,
-                              const void* grads, int grads_are_half, uint32_t* flags);
-/* grads: device float[n], or device fp16[n] when grads_are_half != 0 (the buffer a compressed
- * all-reduce leaves behind: no cast-back pass). */
-/* hyper_dev (nullable): device float[3] = {lr, 1 - beta1^step, sqrt(1 - beta2^step)} overriding the
- * by-value arguments, so that a captured hipGraph of the step can be replayed with new values. */
-/* dst[i] = host_values[i] for n <= 16 floats; the values travel as kernel arguments (no host buffer
- * has to stay alive), used to refresh per-step scalars ahead of a graph replay. */
-int nvo_write_floats(nvo_stream_t stream, float* dst, uint32_t n, const float* host_values);
-/* *flag = any(!isfinite(grads)) */
-int nvo_nonfinite_flag(nvo_stream_t stream, uint64_t n, const void* grads, int grads_are_half, uint32_t* flag);
-/* same check OR-ed into an already initialised flag (several disjoint gradient ranges, one flag) */
-int nvo_nonfinite_flag_or(nvo_stream_t stream, uint64_t n, const void* grads, int grads_are_half, uint32_t* flag);
-/* fp32 -> bfloat16 (round to nearest even; inf / NaN preserved): the compressed form of the gradient exchange.
- * Everywhere a `grads_are_half` argument appears, 0 = fp32, 1 = fp16, 2 = bfloat16. */
-int nvo_cast_bf16(nvo_stream_t stream, uint64_t n, const float* src, void* dst_bf16);
-int nvo_cast_half(nvo_stream_t stream, uint64_t n, const float* src, void* dst_half);
-/* Sharded gradient exchange (multi-GPU: reduce-scatter -> Adam on this rank's 1/world slice -> all-gather of the 16-bit
- * working copy).  src[0, n) is cast to the wire format (1 = fp16, 2 = bf16) as `world` chunks of n / world elements,
- * each followed by `pad` FLAG slots: wire16[(i / per) * (per + pad) + i % per].  *flag (device uint32, OR-ed) is raised
- * when src holds an inf / NaN or a value the SUM over `world` ranks could not carry on the wire (fp16: |v| > 65504 / world
- * -- nothing scans the reduced shard, so a finite sum must follow from the local verdicts; bf16: fp32's range), and every
- * pad slot receives *flag ? 1 : 0 -- after the SUM reduce-scatter of the wire
- * buffer, rank r reads the number of ranks that overflowed from the pad of ITS chunk, so all ranks skip the group
- * together (GradScaler.step semantics) without a second collective: nvo_flag_from_wire ORs (slot != 0) into *flag.
- * n multiple of 4 * world; pad a positive multiple of 4; wire16 holds world * (n / world + pad) elements. */
-int nvo_cast_shards(nvo_stream_t stream, uint64_t n, uint32_t world, uint32_t pad, const float* src, void* wire16,
-                    int wire_fmt, uint32_t* flag);
-int nvo_flag_from_wire(nvo_stream_t stream, const void* wire_slot16, uint32_t* flag);
-/* Clears up to 24 device ranges (host arrays of pointers / byte counts, 4-byte granular) with one launch. */
-int nvo_zero_ranges(nvo_stream_t stream, uint32_t n_ranges, void* const* ptrs, const uint64_t* bytes);
-/* Exponential moving average of the weights, the "Ema" optimiser wrapper of instant-ngp's configs/nerf/base.json
- * (decay 0.95) that pyngp.Testbed trains with (/root/reference/nerf_vo/mapping/instant_ngp.py:45 loads that file):
- * ema = (ema * decay * (1 - decay^(step-1)) + params * (1 - decay)) / (1 - decay^step), step counting from 1; the
- * optional fp16 copy (ema_half) is what inference reads.  skip_flag as in nvo_adam_step. */
-int nvo_ema_update(nvo_stream_t stream, uint64_t n, const float* params, float* ema, void* ema_half, float decay,
-                   uint32_t step, const uint32_t* skip_flag);
-/* The same with the step count on the device: *step_dev = averages applied so far; the call uses t = *step_dev + 1 and
- * advances the counter iff the step was not skipped (the debias factor never runs ahead of the average). */
-/* nvo_ema_update_dev without the commit of the step counter: for callers that average the parameters in several
- * launches (the last one is nvo_ema_update_dev itself). */
-int nvo_ema_update_dev_part(nvo_stream_t stream, uint64_t n, const float* params, float* ema, void* ema_half, float decay,
-                            const uint32_t* step_dev, const uint32_t* skip_flag);
-int nvo_ema_update_dev(nvo_stream_t stream, uint64_t n, const float* params, float* ema, void* ema_half, float decay,
-                       uint32_t* step_dev, const uint32_t* skip_flag);
-/* bf16 MLP mode (BASELINE configs[4]: "MFMA bf16 MLP + fp32 hash accumulate"): the 16-bit working copy of the flat
- * parameter buffer is bfloat16 inside up to 4 element ranges [bf16_lo[k], bf16_hi[k]) (the fused-MLP weights and the
- * appearance embedding; bounds multiples of 4) and fp16 elsewhere (the hash tables).  Host arrays.
- * nvo_adam_step_groups_mixed == nvo_adam_step_groups with that format for the copy it writes. */
-int nvo_cast_working_copy(nvo_stream_t stream, uint64_t n, const float* src, void* dst16, uint32_t n_bf16_ranges,
-                          const uint64_t* bf16_lo, const uint64_t* bf16_hi);
-int nvo_adam_step_groups_mixed(nvo_stream_t stream, uint32_t n_groups, const nvo_adam_group* groups, float* params,
-                               void* params_half, const void* grads, int grads_are_half, float* exp_avg,
-                               float* exp_avg_sq, float beta1, float beta2, float eps, float grad_scale,
-                               float weight_decay, const uint32_t* skip_flags, uint32_t n_bf16_ranges,
-                               const uint64_t* bf16_lo, const uint64_t* bf16_hi);
-/* The same with the loss scale read from the device: loss_scale_dev (nullable) = device float, grad_scale is then
- * 1 / *loss_scale_dev (dynamic loss scaling, the reference trains with mixed_precision=True i.e. torch's GradScaler:
- * /root/reference/nerf_vo/mapping/nerfstudio.py:59). */
-int nvo_adam_step_groups_scaled(nvo_stream_t stream, uint32_t n_groups, const nvo_adam_group* groups, float* params,
-                                void* params_half, const void* grads, int grads_are_half, float* exp_avg,
-                                float* exp_avg_sq, float beta1, float beta2, float eps, float grad_scale,
-                                float weight_decay, const uint32_t* skip_flags, uint32_t n_bf16_ranges,
-                                const uint64_t* bf16_lo, const uint64_t* bf16_hi, const float* loss_scale_dev);
-/* nvo_adam_step_groups_scaled with a TAIL in the same launch (the occupancy-grid trainer's step: four launches less):
- *  - the weight average of exactly the elements the launch steps (nvo_ema_update_dev's arithmetic on the value just
+/* What GradScaler.step / GradScaler.update leave behind, on the device: for every group i in active_mask (bit i),
+ * applied[i] += 1 iff skip_flags[i] == 0, and a group whose counter advances to t gets bias[2 * i] = {1 - beta1^(t+1),
+ * sqrt(1 - beta2^(t+1))} -- what nvo_adam_group::bias_dev of its next step reads; and, when scale != NULL, the loss
+ * scale backs off (x backoff_factor, not below min_scale) if ANY group of scale_mask was skipped and grows
+ * (x growth_factor, not above max_scale) after growth_interval consecutive clean steps (torch defaults: init 65536,
+ * growth 2, backoff 0.5, interval 2000).  (Two masks: a step that runs its optimisers in two launches commits each
+ * launch's counters behind it and updates the scale once, from all of the step's groups.) */
+typedef struct nvo_opt_commit_args {
+    uint32_t n_groups;           /* 1..4 */
+    uint32_t active_mask, scale_mask;
+    uint32_t* applied;           /* device uint32 [n_groups] (nullable: scale only) */
+    const uint32_t* skip_flags;  /* device uint32 [n_groups] (nullable: nothing was skipped) */
+    float* scale;                /* device float (nullable: counters only; the schedule below is then unused) */
+    uint32_t* growth_tracker;    /* device uint32, with scale */
+    float growth_factor, backoff_factor;
+    uint32_t growth_interval;
+    float min_scale, max_scale;
+    float* bias;                 /* device float [n_groups][2] (nullable) */
+    float beta1, beta2;
+} nvo_opt_commit_args;
+/* What may ride behind the groups' step in the SAME launch (the occupancy-grid trainer's step: four launches less):
+ *  - the weight average of exactly the elements the launch steps (nvo_ema_update's arithmetic on the value just
  *    written; a skipped group is not averaged), and
  *  - by the LAST workgroup of the grid, once every other workgroup has checked in (each has then read the scalars a
- *    commit changes), the step's commit: nvo_opt_commit (applied / scale / bias) and the average's counter (ema_commit
- *    != 0: *ema_step_dev += 1 iff skip_flags[ema_flag_slot] == 0, what nvo_ema_update_dev does behind its launch).
+ *    commit changes), the step's commit: `commit` as nvo_opt_commit would run it (requested iff commit.applied or
+ *    commit.scale is set; its skip_flags, beta1 and beta2 must equal the launch's) and the average's counter
+ *    (ema_commit != 0: *ema_step_dev += 1 iff skip_flags[ema_flag_slot] == 0, what nvo_ema_update does behind its
+ *    launch).
  * done_counter: a device word, zero before the first launch; the launch leaves it zero (graph replay safe).  Should the
  * check-in not arrive at exactly the grid size (a counter left dirty, a stall of ~0.5 s) the launch does NOT commit and
  * sets bit 31 of the word, for good: the host checks it where it reads the step's results (a non-zero word after a
- * synchronised launch = the optimiser state can no longer be trusted).  Each part is
- * optional (NULL pointers = not requested); tail == NULL is nvo_adam_step_groups_scaled.  Measured (EXPERIMENTS.md
- * 9.11): -6 us on the occupancy-grid step; the nerfacto step, whose average-free tail is one commit launch, gains
- * nothing from it and keeps nvo_opt_commit_table. */
+ * synchronised launch = the optimiser state can no longer be trusted).  Each part is optional (NULL pointers = not
+ * requested).  Measured (EXPERIMENTS.md 9.11): -6 us on the occupancy-grid step; the nerfacto step, whose average-free
+ * tail is one commit launch, gains nothing from it and keeps the table form of nvo_opt_commit. */
 typedef struct nvo_adam_tail {
     float* ema;                 /* fp32 average, same origin as params (NULL: no averaging) */
     void* ema_half;             /* fp16 copy of the average (nullable) */
@@ -864,55 +797,98 @@ typedef struct nvo_adam_tail {
     uint32_t ema_flag_slot;     /* word of skip_flags that gates the counter */
     uint32_t ema_commit;        /* != 0: advance *ema_step_dev behind the launch */
     uint32_t* done_counter;
-    uint32_t n_commit_groups, active_mask, scale_mask;   /* as nvo_opt_commit */
-    uint32_t* applied;
-    float* scale;
-    uint32_t* growth_tracker;
-    float growth_factor, backoff_factor;
-    uint32_t growth_interval;
-    float min_scale, max_scale;
-    float* bias;
+    nvo_opt_commit_args commit;
 } nvo_adam_tail;
-int nvo_adam_step_groups_tail(nvo_stream_t stream, uint32_t n_groups, const nvo_adam_group* groups, float* params,
-                              void* params_half, const void* grads, int grads_are_half, float* exp_avg,
-                              float* exp_avg_sq, float beta1, float beta2, float eps, float grad_scale,
-                              float weight_decay, const uint32_t* skip_flags, uint32_t n_bf16_ranges,
-                              const uint64_t* bf16_lo, const uint64_t* bf16_hi, const float* loss_scale_dev,
-                              const nvo_adam_tail* tail);
-/* What GradScaler.step / GradScaler.update leave behind, on the device (one tiny launch behind the optimiser launches
- * of a step, capturable): for every group i in active_mask (bit i), applied[i] += 1 iff skip_flags[i] == 0; and, when
- * scale != NULL, the loss scale backs off (x backoff_factor, not below min_scale) if ANY group of scale_mask was
- * skipped and grows (x growth_factor, not above max_scale) after growth_interval consecutive clean steps (torch
- * defaults: init 65536, growth 2, backoff 0.5, interval 2000).  (Two masks: a step that runs its optimisers in two
- * launches commits each launch's counters behind it and updates the scale once, from all of the step's groups.)
- * applied / skip_flags: device uint32 [n_groups] (nullable); scale: device float, growth_tracker: device uint32 (both
- * nullable together). */
-int nvo_opt_commit(nvo_stream_t stream, uint32_t n_groups, uint32_t active_mask, uint32_t scale_mask, uint32_t* applied,
-                   const uint32_t* skip_flags, float* scale, uint32_t* growth_tracker, float growth_factor,
-                   float backoff_factor, uint32_t growth_interval, float min_scale, float max_scale, float* bias,
-                   float beta1, float beta2);
-/* bias (nullable): device float [n_groups][2]; a group whose counter advances to t gets {1 - beta1^(t+1),
- * sqrt(1 - beta2^(t+1))} -- what nvo_adam_group::bias_dev of its next step reads. */
-/* nvo_opt_commit and nvo_write_floats(dst, n, host_values) in ONE launch: a graph-replayed step ends with its Adam
- * launch and the commit rides in the eager launch that writes the next step's scalars. */
-int nvo_opt_commit_write(nvo_stream_t stream, uint32_t n_groups, uint32_t active_mask, uint32_t scale_mask, uint32_t* applied,
-                         const uint32_t* skip_flags, float* scale, uint32_t* growth_tracker, float growth_factor,
-                         float backoff_factor, uint32_t growth_interval, float min_scale, float max_scale, float* bias,
-                         float beta1, float beta2, float* dst, uint32_t n, const float* host_values);
-/* The same as a node INSIDE a captured step: the scalars come from a device table the host fills ahead -- row
- * (s % table_rows) holds the 16 scalars of step s -- and *next_step (device uint32) names the row to load and is
- * advanced by one.  Nothing of the launch depends on host values, so every replay of the graph commits and loads the
- * right row (replaces the eager nvo_opt_commit_write behind each replay: no launch latency behind the graph). */
+/* What all groups of a launch share.  grads are multiplied by grad_scale first (1 / loss scale), or by
+ * 1 / *loss_scale_dev when that device float is given (dynamic loss scaling).  skip_flags: device uint32 [4] or NULL;
+ * a group is a no-op when skip_flags[its flag_slot] != 0 -- GradScaler.step decides per optimiser.  The 16-bit working
+ * copy the launch writes (params_half) is bfloat16 inside up to 4 element ranges [bf16_lo[k], bf16_hi[k]) of the flat
+ * buffer (host arrays, bounds multiples of 4: the fused-MLP weights and the appearance embedding in bf16 MLP mode) and
+ * fp16 elsewhere (the hash tables). */
+typedef struct nvo_adam_args {
+    float* params;
+    void* params_half;            /* nullable */
+    const void* grads;
+    int grads_fmt;
+    float* exp_avg;
+    float* exp_avg_sq;
+    float beta1, beta2, eps, grad_scale;
+    const uint32_t* skip_flags;   /* nullable */
+    const float* loss_scale_dev;  /* nullable */
+    uint32_t n_bf16_ranges;
+    const uint64_t* bf16_lo;
+    const uint64_t* bf16_hi;
+} nvo_adam_args;
+/* One fused pass over 1..4 parameter groups of ONE flat buffer: reads grad / exp_avg / exp_avg_sq / master weight,
+ * writes the moments, the master weight and, if params_half != NULL, the 16-bit working copy.  tail (nullable): see
+ * nvo_adam_tail. */
+int nvo_adam_step(nvo_stream_t stream, const nvo_adam_args* args, uint32_t n_groups, const nvo_adam_group* groups,
+                  const nvo_adam_tail* tail);
+/* The per-step scalars that travel with a commit: dst[0..n) = host_values[0..n) (by value, n <= 16: no host buffer has
+ * to stay alive), or, with table != NULL, dst[0..16) = row (*next_step % table_rows) of a device table of 16-float rows
+ * the host fills ahead (row s % table_rows = the scalars of step s; n == 16, host_values NULL), *next_step (device
+ * uint32) advanced by one. */
+typedef struct nvo_step_scalars {
+    float* dst;
+    uint32_t n;
+    const float* host_values;
+    const float* table;
+    uint32_t table_rows;
+    uint32_t* next_step;
+} nvo_step_scalars;
+/* The commit of nvo_opt_commit_args in one tiny launch behind the optimiser launches of a step (capturable).  scalars
+ * (nullable: commit only) rides in the same launch: by value, a graph-replayed step ends with its Adam launch and the
+ * commit travels in the eager launch that writes the next step's scalars; from the table, nothing of the launch depends
+ * on host values, so the commit can be the last node INSIDE a captured step and every replay commits and loads the
+ * right row (no launch latency behind the graph). */
+int nvo_opt_commit(nvo_stream_t stream, const nvo_opt_commit_args* args, const nvo_step_scalars* scalars);
+/* Non-finite scan of 1..8 spans (element offsets / sizes, host arrays) of one gradient buffer in one launch:
+ * flags[slots[i]] |= 1 iff span i holds an inf / NaN (several spans may share a word); slots == NULL: span i raises
+ * flags[i].  reset != 0 clears flags[0..n_spans) first and requires slots == NULL; reset == 0 ORs into words the caller
+ * cleared earlier (e.g. with the step's nvo_zero_ranges: one launch less in front of the optimiser). */
+int nvo_nonfinite_flag(nvo_stream_t stream, uint32_t n_spans, const uint64_t* offsets, const uint64_t* sizes,
+                       const uint32_t* slots, const void* grads, int grads_fmt, uint32_t* flags, int reset);
+/* Exponential moving average of the weights, the "Ema" optimiser wrapper of instant-ngp's configs/nerf/base.json
+ * (decay 0.95) that pyngp.Testbed trains with:
+ * ema = (ema * decay * (1 - decay^(t-1)) + params * (1 - decay)) / (1 - decay^t) with t = *step_dev + 1, *step_dev
+ * (device uint32) = averages applied so far; the optional fp16 copy (ema_half) is what inference reads.  skip_flag
+ * (device uint32 or NULL): non-zero = the optimiser step was skipped, the average and the counter keep their values
+ * (the debias factor never runs ahead of the average).  commit != 0 advances *step_dev behind the launch; a caller that
+ * averages the parameters in several launches commits with the last one. */
+int nvo_ema_update(nvo_stream_t stream, uint64_t n, const float* params, float* ema, void* ema_half, float decay,
+                   uint32_t* step_dev, const uint32_t* skip_flag, int commit);
+/* dst[i] = host_values[i] for n <= 16 floats; the values travel as kernel arguments (no host buffer
+ * has to stay alive), used to refresh per-step scalars ahead of a graph replay. */
+int nvo_write_floats(nvo_stream_t stream, float* dst, uint32_t n, const float* host_values);
+/* fp32 -> bfloat16 (round to nearest even; inf / NaN preserved): the compressed form of the gradient exchange. */
+int nvo_cast_bf16(nvo_stream_t stream, uint64_t n, const float* src, void* dst_bf16);
+/* fp32 -> fp16 */
+int nvo_cast_half(nvo_stream_t stream, uint64_t n, const float* src, void* dst_half);
+/* fp32 -> the 16-bit working copy of the flat parameter buffer in the mixed format of nvo_adam_args (bf16 MLP mode,
+ * BASELINE configs[4]: "MFMA bf16 MLP + fp32 hash accumulate"): bfloat16 inside the given ranges, fp16 elsewhere. */
+int nvo_cast_working_copy(nvo_stream_t stream, uint64_t n, const float* src, void* dst16, uint32_t n_bf16_ranges,
+                          const uint64_t* bf16_lo, const uint64_t* bf16_hi);
+/* Sharded gradient exchange (multi-GPU: reduce-scatter -> Adam on this rank's 1/world slice -> all-gather of the 16-bit
+ * working copy).  src[0, n) is cast to the wire format (1 = fp16, 2 = bf16) as `world` chunks of n / world elements,
+ * each followed by `pad` FLAG slots: wire16[(i / per) * (per + pad) + i % per].  *flag (device uint32, OR-ed) is raised
+ * when src holds an inf / NaN or a value the SUM over `world` ranks could not carry on the wire (fp16: |v| > 65504 / world
+ * -- nothing scans the reduced shard, so a finite sum must follow from the local verdicts; bf16: fp32's range), and every
+ * pad slot receives *flag ? 1 : 0 -- after the SUM reduce-scatter of the wire buffer, rank r reads the number of ranks
+ * that overflowed from the pad of ITS chunk, so all ranks skip the group together (GradScaler.step semantics) without a
+ * second collective.  n multiple of 4 * world; pad a positive multiple of 4; wire16 holds world * (n / world + pad)
+ * elements. */
+int nvo_cast_shards(nvo_stream_t stream, uint64_t n, uint32_t world, uint32_t pad, const float* src, void* wire16,
+                    int wire_fmt, uint32_t* flag);
+/* *flag |= (the reduced pad slot at wire_slot16 != 0): the verdict nvo_cast_shards sent through the exchange. */
+int nvo_flag_from_wire(nvo_stream_t stream, const void* wire_slot16, uint32_t* flag);
+/* Clears up to 24 device ranges (host arrays of pointers / byte counts, 4-byte granular) with one launch. */
+int nvo_zero_ranges(nvo_stream_t stream, uint32_t n_ranges, void* const* ptrs, const uint64_t* bytes);
 /* Sums the copies a fused-MLP backward spread its weight-gradient adds over (module options "dw_replicas_ptr" /
  * "dw_replicas", nvo_color_args::dw_replicas) into the gradient buffers and clears the copies: for entry i,
  * dst[i][e] += sum_r replicas[i][r * n[i] + e], replicas[i][...] = 0.  One launch for up to 8 networks, behind their
  * backwards and in front of whatever consumes the gradient (exchange, optimiser). */
 int nvo_fold_replicas(nvo_stream_t stream, uint32_t n_entries, float* const* replicas, const uint32_t* n_replicas,
                       const uint64_t* n, float* const* dst);
-int nvo_opt_commit_table(nvo_stream_t stream, uint32_t n_groups, uint32_t active_mask, uint32_t scale_mask, uint32_t* applied,
-                         const uint32_t* skip_flags, float* scale, uint32_t* growth_tracker, float growth_factor,
-                         float backoff_factor, uint32_t growth_interval, float min_scale, float max_scale, float* bias,
-                         float beta1, float beta2, float* dst, const float* table, uint32_t table_rows, uint32_t* next_step);
 
 /* ------------------------------------------------------------------------------------------------
  * G. Keyframe depth alignment (the producer right before the mapping path; replaces the torch-op chain of

@@ -83,20 +83,34 @@ class FusedAdamArgs(C.Structure):
 
 
 class AdamGroup(C.Structure):
-    """nvo_adam_group (include/nerfvo_hip.h)"""
-    _fields_ = [("offset", C.c_uint64), ("n", C.c_uint64), ("lr", C.c_float), ("step", C.c_uint32),
-                ("hyper_dev", C.c_void_p), ("bias_dev", C.c_void_p), ("flag_slot", C.c_uint32),
-                ("flag_slot_set", C.c_uint32), ("weight_decay", C.c_float), ("weight_decay_set", C.c_uint32)]
+    """mirror of nvo_adam_group"""
+    _fields_ = [("offset", _u64), ("n", _u64), ("lr", _f), ("step", _u32), ("hyper_dev", _p), ("bias_dev", _p),
+                ("flag_slot", _u32), ("weight_decay", _f)]
+
+
+class OptCommitArgs(C.Structure):
+    """mirror of nvo_opt_commit_args"""
+    _fields_ = [("n_groups", _u32), ("active_mask", _u32), ("scale_mask", _u32), ("applied", _p), ("skip_flags", _p),
+                ("scale", _p), ("growth_tracker", _p), ("growth_factor", _f), ("backoff_factor", _f),
+                ("growth_interval", _u32), ("min_scale", _f), ("max_scale", _f), ("bias", _p), ("beta1", _f), ("beta2", _f)]
 
 
 class AdamTail(C.Structure):
-    """nvo_adam_tail (include/nerfvo_hip.h)"""
-    _fields_ = [("ema", C.c_void_p), ("ema_half", C.c_void_p), ("ema_decay", C.c_float), ("ema_step_dev", C.c_void_p),
-                ("ema_flag_slot", C.c_uint32), ("ema_commit", C.c_uint32), ("done_counter", C.c_void_p),
-                ("n_commit_groups", C.c_uint32), ("active_mask", C.c_uint32), ("scale_mask", C.c_uint32),
-                ("applied", C.c_void_p), ("scale", C.c_void_p), ("growth_tracker", C.c_void_p),
-                ("growth_factor", C.c_float), ("backoff_factor", C.c_float), ("growth_interval", C.c_uint32),
-                ("min_scale", C.c_float), ("max_scale", C.c_float), ("bias", C.c_void_p)]
+    """mirror of nvo_adam_tail"""
+    _fields_ = [("ema", _p), ("ema_half", _p), ("ema_decay", _f), ("ema_step_dev", _p), ("ema_flag_slot", _u32),
+                ("ema_commit", _u32), ("done_counter", _p), ("commit", OptCommitArgs)]
+
+
+class AdamArgs(C.Structure):
+    """mirror of nvo_adam_args"""
+    _fields_ = [("params", _p), ("params_half", _p), ("grads", _p), ("grads_fmt", _int), ("exp_avg", _p),
+                ("exp_avg_sq", _p), ("beta1", _f), ("beta2", _f), ("eps", _f), ("grad_scale", _f), ("skip_flags", _p),
+                ("loss_scale_dev", _p), ("n_bf16_ranges", _u32), ("bf16_lo", _p), ("bf16_hi", _p)]
+
+
+class StepScalars(C.Structure):
+    """mirror of nvo_step_scalars"""
+    _fields_ = [("dst", _p), ("n", _u32), ("host_values", _p), ("table", _p), ("table_rows", _u32), ("next_step", _p)]
 
 
 class DepthAlignArgs(C.Structure):
@@ -234,33 +248,21 @@ _SIGNATURES = {
     # group I
     "nvo_nn_query": (_int, [_p, C.POINTER(NnArgs)]),
     # group E
-    "nvo_adam_step": (_int, [_p, _u64, _p, _p, _p, _int, _p, _p, _f, _f, _f, _f, _u32, _f, _f, _p, _p]),
+    "nvo_adam_step": (_int, [_p, C.POINTER(AdamArgs), _u32, C.POINTER(AdamGroup), C.POINTER(AdamTail)]),
+    "nvo_opt_commit": (_int, [_p, C.POINTER(OptCommitArgs), C.POINTER(StepScalars)]),
+    "nvo_nonfinite_flag": (_int, [_p, _u32, _p, _p, _p, _p, _int, _p, _int]),
+    "nvo_ema_update": (_int, [_p, _u64, _p, _p, _p, _f, _p, _p, _int]),
     "nvo_write_floats": (_int, [_p, _p, _u32, _p]),
-    "nvo_nonfinite_flag": (_int, [_p, _u64, _p, _int, _p]),
-    "nvo_nonfinite_flag_or": (_int, [_p, _u64, _p, _int, _p]),
-    "nvo_adam_step_groups": (_int, [_p, _u32, _p, _p, _p, _p, _int, _p, _p, _f, _f, _f, _f, _f, _p]),
-    "nvo_nonfinite_flag_ranges": (_int, [_p, _u32, _p, _p, _p, _int, _p]),
-    "nvo_nonfinite_flag_ranges_or": (_int, [_p, _u32, _p, _p, _p, _int, _p]),
-    "nvo_nonfinite_flag_spans_or": (_int, [_p, _u32, _p, _p, _p, _p, _int, _p]),
     "nvo_cast_half": (_int, [_p, _u64, _p, _p]),
+    "nvo_cast_bf16": (_int, [_p, _u64, _p, _p]),
+    "nvo_cast_working_copy": (_int, [_p, _u64, _p, _p, _u32, _p, _p]),
+    "nvo_cast_shards": (_int, [_p, _u64, _u32, _u32, _p, _p, _int, _p]),
+    "nvo_flag_from_wire": (_int, [_p, _p, _p]),
     "nvo_zero_ranges": (_int, [_p, _u32, _p, _p]),
     "nvo_bwd_zero_ranges": (_int, [_p, _p, _p, _p, _u32]),
     "nvo_fold_replicas": (_int, [_p, _u32, _p, _p, _p, _p]),
     "nvo_fused_adam_range": (_int, [_p, _p, _p]),
     "nvo_set_fused_adam": (_int, [_p, _p]),
-    "nvo_ema_update": (_int, [_p, _u64, _p, _p, _p, _f, _u32, _p]),
-    "nvo_ema_update_dev": (_int, [_p, _u64, _p, _p, _p, _f, _p, _p]),
-    "nvo_ema_update_dev_part": (_int, [_p, _u64, _p, _p, _p, _f, _p, _p]),
-    "nvo_cast_working_copy": (_int, [_p, _u64, _p, _p, _u32, _p, _p]),
-    "nvo_adam_step_groups_mixed": (_int, [_p, _u32, _p, _p, _p, _p, _int, _p, _p, _f, _f, _f, _f, _f, _p, _u32, _p, _p]),
-    "nvo_adam_step_groups_scaled": (_int, [_p, _u32, _p, _p, _p, _p, _int, _p, _p, _f, _f, _f, _f, _f, _p, _u32, _p, _p, _p]),
-    "nvo_adam_step_groups_tail": (_int, [_p, _u32, _p, _p, _p, _p, _int, _p, _p, _f, _f, _f, _f, _f, _p, _u32, _p, _p, _p, _p]),
-    "nvo_opt_commit_write": (_int, [_p, _u32, _u32, _u32, _p, _p, _p, _p, _f, _f, _u32, _f, _f, _p, _f, _f, _p, _u32, _p]),
-    "nvo_opt_commit_table": (_int, [_p, _u32, _u32, _u32, _p, _p, _p, _p, _f, _f, _u32, _f, _f, _p, _f, _f, _p, _p, _u32, _p]),
-    "nvo_opt_commit": (_int, [_p, _u32, _u32, _u32, _p, _p, _p, _p, _f, _f, _u32, _f, _f, _p, _f, _f]),
-    "nvo_cast_bf16": (_int, [_p, _u64, _p, _p]),
-    "nvo_cast_shards": (_int, [_p, _u64, _u32, _u32, _p, _p, _int, _p]),
-    "nvo_flag_from_wire": (_int, [_p, _p, _p]),
 }
 
 

@@ -435,7 +435,7 @@ struct GridModule : nvo_module_s {
         d.beta1 = a->beta1;
         d.beta2 = a->beta2;
         d.eps = a->eps;
-        if (!a->bias_dev) {  // as nvo_adam_step / nvo_adam_step_groups price a host-side step count
+        if (!a->bias_dev) {  // as nvo_adam_step prices a host-side step count
             NVO_REQUIRE(a->step >= 1, "set_fused_adam: step counts from 1 (or pass bias_dev)");
             d.bias1 = 1.f - powf(a->beta1, (float)a->step);
             d.bias2_sqrt = sqrtf(1.f - powf(a->beta2, (float)a->step));

@@ -2463,7 +2463,7 @@ k_tl_accumulate_p(NvoGridLevels g, const uint4* __restrict__ items, uint32_t n_i
     // fused optimiser step (NvoGridAdam): the scalars of this launch, read once
     NvoAdamHyper ah{adam.lr, adam.beta1, adam.beta2, adam.eps, adam.bias1, adam.bias2_sqrt, adam.grad_scale, 0.f};
     bool adam_skip = false;
-    float ema_keep = 0.f, ema_take = 0.f, ema_inv = 1.f;  // (k_ema_update_dev's factors, same expressions)
+    float ema_keep = 0.f, ema_take = 0.f, ema_inv = 1.f;  // (k_ema_update's factors, same expressions)
     if (adam.params && adam.ema) {
         const double d = (double)adam.ema_decay, t = (double)(*adam.ema_step_dev) + 1.0;
         ema_keep = (float)(d * (1.0 - pow(d, t - 1.0)));

@@ -153,8 +153,8 @@ class EngineConfig:
     # the graph but rides in the eager launch behind the replay that also writes the NEXT step's scalars
     commit_behind_replay: bool = True
     # ... or (takes precedence) IS the last node of the graph and takes the next step's scalars from a device table the
-    # host fills 1024 steps ahead (nvo_opt_commit_table): nothing eager behind the replay -- the trace showed 8 us of
-    # launch latency between the graph's last kernel and the eager launch, plus its 5 us, on every step
+    # host fills 1024 steps ahead (the table form of nvo_opt_commit): nothing eager behind the replay -- the trace showed
+    # 8 us of launch latency between the graph's last kernel and the eager launch, plus its 5 us, on every step
     commit_from_table: bool = True
     # one-graph step (single GPU): the tile-local accumulate pass of the main grid applies Adam to the entries of the
     # hashed levels it has just summed (nvo_set_fused_adam) instead of storing their gradient -- 8 B of HBM traffic per
@@ -1168,8 +1168,7 @@ class NerfactoEngine:
         cfg = self.cfg
         stream = _stream(self.device)
         # grads_half: the 2-byte (bf16 | fp16) buffer a compressed all-reduce left behind -- consumed directly
-        gbuf, gsz, ghalf = (self.grads, 4, 0) if grads_half is None else (
-            grads_half, 2, 2 if grads_half.dtype == torch.bfloat16 else 1)
+        gbuf, gfmt = (self.grads, 0) if grads_half is None else (grads_half, 2 if grads_half.dtype == torch.bfloat16 else 1)
         active = [g for g in groups if g != "camera_opt" or cfg.optimize_poses]
         order = self._GROUP_ORDER
 
@@ -1204,7 +1203,7 @@ class NerfactoEngine:
                 offs = (C.c_uint64 * len(spans))(*[sp[0] for sp in spans])
                 sizes = (C.c_uint64 * len(spans))(*[sp[1] for sp in spans])
                 slots = (C.c_uint32 * len(spans))(*[sp[2] for sp in spans])
-                _call("nvo_nonfinite_flag_spans_or", stream, len(spans), offs, sizes, slots, _ptr(gbuf), ghalf, _ptr(self.skip_flag))
+                _call("nvo_nonfinite_flag", stream, len(spans), offs, sizes, slots, _ptr(gbuf), gfmt, _ptr(self.skip_flag), 0)
         elif check:
             # one flag PER GROUP that trains this step (GradScaler.step decides per optimiser; ranges of idle groups
             # hold stale values and are neither checked nor applied), all in one launch; flag word = the group's slot
@@ -1215,7 +1214,7 @@ class NerfactoEngine:
                 slots = [order.index(g) for g in active]
                 for sl in slots:  # only the words of the groups checked here (another call may own the others)
                     _call("nvo_zero_ranges", stream, 1, (C.c_void_p * 1)(self.skip_flag.data_ptr() + 4 * sl), (C.c_uint64 * 1)(4))
-            _call("nvo_nonfinite_flag_ranges_or", stream, len(order), offs, sizes, _ptr(gbuf), ghalf, _ptr(self.skip_flag))
+            _call("nvo_nonfinite_flag", stream, len(order), offs, sizes, None, _ptr(gbuf), gfmt, _ptr(self.skip_flag), 0)
         batch = []
         mask = 0
         fused = getattr(self, "_fused_adam_range", None)  # (set around the capture of the one-graph step)
@@ -1232,15 +1231,18 @@ class NerfactoEngine:
             for a_, b_ in parts:
                 if b_ > a_:
                     batch.append(_lib.AdamGroup(offset=a_, n=b_ - a_, lr=self._group_lr(g), step=0, hyper_dev=hyper,
-                                                bias_dev=self.dev_bias.data_ptr() + 8 * gi, flag_slot=gi, flag_slot_set=1))
+                                                bias_dev=self.dev_bias.data_ptr() + 8 * gi, flag_slot=gi))
         if not batch:
             return
         arr = (_lib.AdamGroup * len(batch))(*batch)
         dyn = cfg.dynamic_loss_scale
-        _call("nvo_adam_step_groups_scaled", stream, len(batch), arr, _ptr(self.params), _ptr(self.params_half), _ptr(gbuf),
-              ghalf, _ptr(self.exp_avg), _ptr(self.exp_avg_sq), cfg.adam_betas[0], cfg.adam_betas[1], cfg.adam_eps,
-              1.0 / cfg.loss_scale, 0.0, _ptr(self.skip_flag), len(self.bf16_ranges), self._bf16_lo, self._bf16_hi,
-              _ptr(self.dev_loss_scale) if dyn else None)
+        args = _lib.AdamArgs(
+            params=self.params.data_ptr(), params_half=self.params_half.data_ptr(), grads=gbuf.data_ptr(), grads_fmt=gfmt,
+            exp_avg=self.exp_avg.data_ptr(), exp_avg_sq=self.exp_avg_sq.data_ptr(), beta1=cfg.adam_betas[0],
+            beta2=cfg.adam_betas[1], eps=cfg.adam_eps, grad_scale=1.0 / cfg.loss_scale, skip_flags=self.skip_flag.data_ptr(),
+            loss_scale_dev=self.dev_loss_scale.data_ptr() if dyn else None, n_bf16_ranges=len(self.bf16_ranges),
+            bf16_lo=C.addressof(self._bf16_lo), bf16_hi=C.addressof(self._bf16_hi))
+        _call("nvo_adam_step", stream, C.byref(args), len(batch), arr, None)
         scale_mask = 0
         if dyn and "fields" in active:  # the fields group is stepped last in every launch order
             for g in (step_groups if step_groups is not None else active):
@@ -1250,10 +1252,18 @@ class NerfactoEngine:
             # (capture of the one-graph step: the commit rides in the eager launch behind the replay, _commit_and_write)
             self._defer_commit.append((mask, scale_mask))
             return
-        _call("nvo_opt_commit", stream, len(order), mask, scale_mask, _ptr(self.dev_applied), _ptr(self.skip_flag),
-              _ptr(self.dev_loss_scale) if scale_mask else None, _ptr(self.dev_growth_tracker) if scale_mask else None,
-              cfg.loss_scale_growth, cfg.loss_scale_backoff, int(cfg.loss_scale_interval), cfg.loss_scale_min, cfg.loss_scale_max,
-              _ptr(self.dev_bias), cfg.adam_betas[0], cfg.adam_betas[1])
+        _call("nvo_opt_commit", stream, C.byref(self._commit_args(mask, scale_mask)), None)
+
+    def _commit_args(self, mask: int, scale_mask: int) -> "_lib.OptCommitArgs":
+        """nvo_opt_commit_args of this engine: the counters of the groups in ``mask`` and, with a non-zero
+        ``scale_mask``, the loss-scale update from those groups' flags."""
+        cfg = self.cfg
+        return _lib.OptCommitArgs(
+            n_groups=len(self._GROUP_ORDER), active_mask=mask, scale_mask=scale_mask, applied=self.dev_applied.data_ptr(),
+            skip_flags=self.skip_flag.data_ptr(), scale=self.dev_loss_scale.data_ptr() if scale_mask else None,
+            growth_tracker=self.dev_growth_tracker.data_ptr() if scale_mask else None, growth_factor=cfg.loss_scale_growth,
+            backoff_factor=cfg.loss_scale_backoff, growth_interval=int(cfg.loss_scale_interval), min_scale=cfg.loss_scale_min,
+            max_scale=cfg.loss_scale_max, bias=self.dev_bias.data_ptr(), beta1=cfg.adam_betas[0], beta2=cfg.adam_betas[1])
 
     def _fused_adam_plan(self):
         """(lo, hi) of the flat parameter buffer whose Adam step the main grid's backward can take over
@@ -1297,8 +1307,8 @@ class NerfactoEngine:
     _TABLE_ROWS = 1024
 
     def _scalar_table(self):
-        """Device ring of the per-step scalars (row s % 1024 = _scalar_row(s)) + the step counter nvo_opt_commit_table
-        advances; see EngineConfig.commit_from_table."""
+        """Device ring of the per-step scalars (row s % 1024 = _scalar_row(s)) + the step counter the table form of
+        nvo_opt_commit advances; see EngineConfig.commit_from_table."""
         if getattr(self, "dev_scalar_table", None) is None:
             self.dev_scalar_table = torch.zeros(self._TABLE_ROWS, 16, dtype=torch.float32, device=self.device)
             self.dev_next_step = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -1333,25 +1343,19 @@ class NerfactoEngine:
         self._table_valid = (s, s + self._TABLE_ROWS, stamp)
 
     def _launch_commit_table(self, mask: int, scale_mask: int) -> None:
-        cfg = self.cfg
-        _call("nvo_opt_commit_table", _stream(self.device), len(self._GROUP_ORDER), mask, scale_mask, _ptr(self.dev_applied),
-              _ptr(self.skip_flag), _ptr(self.dev_loss_scale) if scale_mask else None,
-              _ptr(self.dev_growth_tracker) if scale_mask else None, cfg.loss_scale_growth, cfg.loss_scale_backoff,
-              int(cfg.loss_scale_interval), cfg.loss_scale_min, cfg.loss_scale_max, _ptr(self.dev_bias), cfg.adam_betas[0],
-              cfg.adam_betas[1], _ptr(self.dev_scalars), _ptr(self.dev_scalar_table), self._TABLE_ROWS, _ptr(self.dev_next_step))
+        scalars = _lib.StepScalars(dst=self.dev_scalars.data_ptr(), n=16, host_values=None,
+                                   table=self.dev_scalar_table.data_ptr(), table_rows=self._TABLE_ROWS,
+                                   next_step=self.dev_next_step.data_ptr())
+        _call("nvo_opt_commit", _stream(self.device), C.byref(self._commit_args(mask, scale_mask)), C.byref(scalars))
 
     def _commit_and_write(self, masks, sampling_step: int) -> None:
         """GradScaler.update + step counters of the step that just replayed AND the scalars of step ``sampling_step`` (=
-        self.step, already advanced) in one eager launch (nvo_opt_commit_write)."""
-        cfg = self.cfg
+        self.step, already advanced) in one eager launch (nvo_opt_commit with by-value scalars)."""
         mask, scale_mask = masks
         vals = self._scalar_values(self.anneal_at(sampling_step), sampling_step)
         arr = (C.c_float * 16)(*vals)
-        _call("nvo_opt_commit_write", _stream(self.device), len(self._GROUP_ORDER), mask, scale_mask, _ptr(self.dev_applied),
-              _ptr(self.skip_flag), _ptr(self.dev_loss_scale) if scale_mask else None,
-              _ptr(self.dev_growth_tracker) if scale_mask else None, cfg.loss_scale_growth, cfg.loss_scale_backoff,
-              int(cfg.loss_scale_interval), cfg.loss_scale_min, cfg.loss_scale_max, _ptr(self.dev_bias), cfg.adam_betas[0], cfg.adam_betas[1],
-              _ptr(self.dev_scalars), 16, arr)
+        scalars = _lib.StepScalars(dst=self.dev_scalars.data_ptr(), n=16, host_values=C.addressof(arr))
+        _call("nvo_opt_commit", _stream(self.device), C.byref(self._commit_args(mask, scale_mask)), C.byref(scalars))
         self._scalars_step = sampling_step
 
     # ------------------------------------------------------------------------------------------

@@ -119,8 +119,8 @@ class NgpConfig:
     # single GPU: the grid backward takes the Adam step + weight average of its streamed hashed levels itself
     # (nvo_set_fused_adam; bit-identical to the separate launches)
     fuse_grid_adam: bool = True
-    # the weight average and the step's commit ride in the Adam launch (nvo_adam_step_groups_tail; bit-identical to the
-    # four launches it replaces: two nvo_ema_update_dev, k_ema_commit, nvo_opt_commit)
+    # the weight average and the step's commit ride in the Adam launch (nvo_adam_tail; bit-identical to the
+    # four launches it replaces: two nvo_ema_update, k_ema_commit, nvo_opt_commit)
     fuse_optimizer_tail: bool = True
     # copies of the two MLPs' weight-gradient buffers the backward's workgroups spread their adds over (0 = off;
     # nvo_fold_replicas sums them once per step)
@@ -223,7 +223,7 @@ class NgpEngine:
         self.step = 0
         self.opt_step = 0
         # device side of the optimiser's step count: [0] = learning rate (unused: by value), [1..2] = {1 - beta1^t,
-        # sqrt(1 - beta2^t)} of the NEXT applied step (nvo_adam_step's hyper_dev layout; [1..2] alone = nvo_adam_group::bias_dev), advanced by
+        # sqrt(1 - beta2^t)} of the NEXT applied step (nvo_adam_group::hyper_dev's layout; [1..2] alone = nvo_adam_group::bias_dev), advanced by
         # nvo_opt_commit behind the optimiser launches iff the step was not skipped -- nothing of a step depends on a host
         # scalar, so a captured step can be replayed
         self._opt_dev = z(4)
@@ -236,7 +236,7 @@ class NgpEngine:
         self._cam_synced = None    # (cam_step, lr) the device scalars were written for
         self._cam_window = 0       # training steps accumulated into d_corrections since the last camera update
         self._applied_dev = z(1, torch.int32)
-        self._tail_done = z(1, torch.int32)  # check-in counter of nvo_adam_step_groups_tail (the launch leaves it zero)
+        self._tail_done = z(1, torch.int32)  # check-in counter of nvo_adam_tail (the launch leaves it zero)
         self._dev_synced = None   # the host opt_step the two buffers above were written for
         self._graphs = {}         # captured steps by (ray count, inputs' addresses, ...)
         self._kernels_loaded = False
@@ -781,15 +781,31 @@ class NgpEngine:
         if all_reduce is not None:
             all_reduce(self.pose_grads)
         n6 = cfg.num_images * 6
-        _call("nvo_nonfinite_flag", stream, n6, _ptr(self.pose_grads), 0, _ptr(self._cam_flag))
-        _call("nvo_adam_step", stream, n6, _ptr(self.pose_adjustment), _ptr(self._pose_half), _ptr(self.pose_grads), 0,
-              _ptr(self.pose_exp_avg), _ptr(self.pose_exp_avg_sq), cfg.extrinsic_lr, cfg.adam_betas[0],
-              cfg.adam_betas[1], cfg.adam_eps, 1, scale, 0.0, _ptr(self._cam_flag), _ptr(self._cam_dev))
-        # (hyper_dev = self._cam_dev overrides the by-value learning rate and step)
-        _call("nvo_opt_commit", stream, 1, 1, 0, _ptr(self._cam_applied_dev), _ptr(self._cam_flag), None, None, 2.0, 0.5,
-              2000, 0.0, 0.0, C.c_void_p(self._cam_dev.data_ptr() + 4), cfg.adam_betas[0], cfg.adam_betas[1])
+        _call("nvo_nonfinite_flag", stream, 1, (C.c_uint64 * 1)(0), (C.c_uint64 * 1)(n6), None, _ptr(self.pose_grads), 0,
+              _ptr(self._cam_flag), 1)
+        # (hyper_dev = self._cam_dev carries the learning rate and the bias corrections of the camera optimiser's own count)
+        group = _lib.AdamGroup(offset=0, n=n6, lr=cfg.extrinsic_lr, step=1, hyper_dev=self._cam_dev.data_ptr(), bias_dev=None,
+                               flag_slot=0, weight_decay=0.0)
+        args = self._adam_args(self.pose_adjustment, self._pose_half, self.pose_grads, self.pose_exp_avg, self.pose_exp_avg_sq,
+                               scale, self._cam_flag)
+        _call("nvo_adam_step", stream, C.byref(args), 1, C.byref(group), None)
+        commit = self._counter_commit(self._cam_applied_dev, self._cam_flag, self._cam_dev.data_ptr() + 4)
+        _call("nvo_opt_commit", stream, C.byref(commit), None)
         _call("nvo_zero_ranges", stream, 1, (C.c_void_p * 1)(self.d_corrections.data_ptr()),
               (C.c_uint64 * 1)(4 * self.d_corrections.numel()))
+
+    def _adam_args(self, params, params_half, grads, exp_avg, exp_avg_sq, grad_scale: float, flag) -> "_lib.AdamArgs":
+        cfg = self.cfg
+        return _lib.AdamArgs(params=params.data_ptr(), params_half=params_half.data_ptr(), grads=grads.data_ptr(), grads_fmt=0,
+                             exp_avg=exp_avg.data_ptr(), exp_avg_sq=exp_avg_sq.data_ptr(), beta1=cfg.adam_betas[0],
+                             beta2=cfg.adam_betas[1], eps=cfg.adam_eps, grad_scale=grad_scale, skip_flags=flag.data_ptr())
+
+    def _counter_commit(self, applied, flag, bias_ptr: int) -> "_lib.OptCommitArgs":
+        """nvo_opt_commit_args of one optimiser without a dynamic loss scale: its applied-step counter and the bias
+        corrections of its next step, iff ``flag`` is clear."""
+        cfg = self.cfg
+        return _lib.OptCommitArgs(n_groups=1, active_mask=1, scale_mask=0, applied=applied.data_ptr(), skip_flags=flag.data_ptr(),
+                                  bias=bias_ptr, beta1=cfg.adam_betas[0], beta2=cfg.adam_betas[1])
 
     def _fused_adam_plan(self):
         """(lo, hi) of the flat parameter buffer the grid backward can step itself (its streamed hashed levels), or None.
@@ -852,17 +868,21 @@ class NgpEngine:
         self._sync_opt_dev()
         bias_dev = self._opt_dev.data_ptr() + 4
         if not self._leaf_flags:
-            _call("nvo_nonfinite_flag", stream, self.n_params, _ptr(self.grads), 0, _ptr(self.skip_flag))
+            _call("nvo_nonfinite_flag", stream, 1, (C.c_uint64 * 1)(0), (C.c_uint64 * 1)(self.n_params), None, _ptr(self.grads),
+                  0, _ptr(self.skip_flag), 1)
         n_grid = self.density_net.n_params - self.n_density_mlp
         if fused_adam is not None:  # (the backward stepped [fused_adam): the tail of the grid's range)
             assert self.n_density_mlp <= fused_adam[0] and fused_adam[1] == self.density_net.n_params
             n_grid = fused_adam[0] - self.n_density_mlp
         # (offset, size, weight decay): density MLP | hash grid | rgb MLP -- l2_reg on MLP weights only; ONE launch
         batch = [_lib.AdamGroup(offset=off, n=size, lr=cfg.lr, step=0, hyper_dev=None, bias_dev=bias_dev, flag_slot=0,
-                                flag_slot_set=1, weight_decay=wd, weight_decay_set=1)
+                                weight_decay=wd)
                  for off, size, wd in ((0, self.n_density_mlp, cfg.l2_reg), (self.n_density_mlp, n_grid, 0.0),
                                        (self.density_net.n_params, self.n_rgb, cfg.l2_reg)) if size > 0]
         arr = (_lib.AdamGroup * len(batch))(*batch)
+        args = self._adam_args(self.params, self.params_half, self.grads, self.exp_avg, self.exp_avg_sq, 1.0 / cfg.loss_scale,
+                               self.skip_flag)
+        commit = self._counter_commit(self._applied_dev, self.skip_flag, bias_dev)
         if cfg.ema_decay > 0.0:
             if self.params_ema is None:
                 self.params_ema = torch.zeros_like(self.params)
@@ -872,41 +892,34 @@ class NgpEngine:
             self._ema_started = True
         if cfg.fuse_optimizer_tail:
             # ONE launch: Adam of the three ranges, the weight average of the same elements and -- by its last workgroup --
-            # both counters with the next step's bias corrections (nvo_adam_step_groups_tail)
+            # both counters with the next step's bias corrections (nvo_adam_tail)
             ema = cfg.ema_decay > 0.0
             tail = _lib.AdamTail(ema=self.params_ema.data_ptr() if ema else None,
                                  ema_half=self.params_ema_half.data_ptr() if ema else None, ema_decay=cfg.ema_decay,
                                  ema_step_dev=self._ema_step_dev.data_ptr() if ema else None, ema_flag_slot=0, ema_commit=1,
-                                 done_counter=self._tail_done.data_ptr(), n_commit_groups=1, active_mask=1, scale_mask=0,
-                                 applied=self._applied_dev.data_ptr(), scale=None, growth_tracker=None, growth_factor=2.0,
-                                 backoff_factor=0.5, growth_interval=2000, min_scale=0.0, max_scale=0.0, bias=bias_dev)
-            _call("nvo_adam_step_groups_tail", stream, len(batch), arr, _ptr(self.params), _ptr(self.params_half),
-                  _ptr(self.grads), 0, _ptr(self.exp_avg), _ptr(self.exp_avg_sq), cfg.adam_betas[0], cfg.adam_betas[1],
-                  cfg.adam_eps, 1.0 / cfg.loss_scale, 0.0, _ptr(self.skip_flag), 0, None, None, None, C.byref(tail))
+                                 done_counter=self._tail_done.data_ptr(), commit=commit)
+            _call("nvo_adam_step", stream, C.byref(args), len(batch), arr, C.byref(tail))
             if camera_update and cfg.optimize_extrinsics and self._pose_inputs is not None:
                 self._sync_cam_dev()
                 self._camera_optimizer_step(stream, all_reduce)
             return
-        _call("nvo_adam_step_groups", stream, len(batch), arr, _ptr(self.params), _ptr(self.params_half), _ptr(self.grads), 0,
-              _ptr(self.exp_avg), _ptr(self.exp_avg_sq), cfg.adam_betas[0], cfg.adam_betas[1], cfg.adam_eps,
-              1.0 / cfg.loss_scale, 0.0, _ptr(self.skip_flag))
+        _call("nvo_adam_step", stream, C.byref(args), len(batch), arr, None)
         if cfg.ema_decay > 0.0:
             lo, hi = (0, self.n_params)
             if fused_adam is not None:
                 # the backward averaged [fused_adam) already (with the counter as it stands): the head here without
                 # committing the counter, the tail below with it
-                _call("nvo_ema_update_dev_part", stream, fused_adam[0], _ptr(self.params), _ptr(self.params_ema),
-                      _ptr(self.params_ema_half), cfg.ema_decay, _ptr(self._ema_step_dev), _ptr(self.skip_flag))
+                _call("nvo_ema_update", stream, fused_adam[0], _ptr(self.params), _ptr(self.params_ema),
+                      _ptr(self.params_ema_half), cfg.ema_decay, _ptr(self._ema_step_dev), _ptr(self.skip_flag), 0)
                 lo = fused_adam[1]
-            _call("nvo_ema_update_dev", stream, hi - lo, C.c_void_p(self.params.data_ptr() + 4 * lo),
+            _call("nvo_ema_update", stream, hi - lo, C.c_void_p(self.params.data_ptr() + 4 * lo),
                   C.c_void_p(self.params_ema.data_ptr() + 4 * lo), C.c_void_p(self.params_ema_half.data_ptr() + 2 * lo),
-                  cfg.ema_decay, _ptr(self._ema_step_dev), _ptr(self.skip_flag))
+                  cfg.ema_decay, _ptr(self._ema_step_dev), _ptr(self.skip_flag), 1)
         if camera_update and cfg.optimize_extrinsics and self._pose_inputs is not None:
             self._sync_cam_dev()  # (a no-op once train_step has written them: nothing is uploaded inside a capture)
             self._camera_optimizer_step(stream, all_reduce)
         # the step counter and the next step's bias corrections, behind every launch that read them
-        _call("nvo_opt_commit", stream, 1, 1, 0, _ptr(self._applied_dev), _ptr(self.skip_flag), None, None, 2.0, 0.5, 2000,
-              0.0, 0.0, C.c_void_p(bias_dev), cfg.adam_betas[0], cfg.adam_betas[1])
+        _call("nvo_opt_commit", stream, C.byref(commit), None)
 
     def train_step(self, ray_indices, intrinsics, c2w, images, depths, all_reduce=None, depths_cov=None):
         R = ray_indices.shape[0]

@@ -45,6 +45,37 @@ def _make_engine(device, **over):
     return eng
 
 
+def _adam_step(st, groups, p, p16, grads, grads_fmt, m, v, flag, beta2=0.999, grad_scale=1.0 / 128.0, tail=None):
+    """nvo_adam_step over (offset, n, lr, step, hyper_dev, flag_slot) groups of one flat buffer; ``p`` ... ``flag`` are
+    tensors or raw addresses (p16 / flag may be None)."""
+    import ctypes as C
+
+    from nerf_vo_amd import _lib
+    from nerf_vo_amd.engine import _call
+
+    def addr(t):
+        return t.data_ptr() if torch.is_tensor(t) else t
+
+    args = _lib.AdamArgs(params=addr(p), params_half=addr(p16), grads=addr(grads), grads_fmt=grads_fmt, exp_avg=addr(m),
+                         exp_avg_sq=addr(v), beta1=0.9, beta2=beta2, eps=1e-15, grad_scale=grad_scale, skip_flags=addr(flag))
+    arr = (_lib.AdamGroup * len(groups))(*[
+        _lib.AdamGroup(offset=o, n=n, lr=lr, step=step, hyper_dev=addr(hyper), bias_dev=None, flag_slot=slot, weight_decay=0.0)
+        for o, n, lr, step, hyper, slot in groups])
+    _call("nvo_adam_step", st, C.byref(args), len(groups), arr, None if tail is None else C.byref(tail))
+
+
+def _nonfinite_flag(st, spans, grads, grads_fmt, flags, slots=None, reset=1):
+    """nvo_nonfinite_flag over (offset, n) spans of ``grads`` (a tensor or a raw address)."""
+    import ctypes as C
+
+    from nerf_vo_amd.engine import _call, _ptr
+
+    k = len(spans)
+    _call("nvo_nonfinite_flag", st, k, (C.c_uint64 * k)(*[o for o, _ in spans]), (C.c_uint64 * k)(*[n for _, n in spans]),
+          None if slots is None else (C.c_uint32 * k)(*slots), _ptr(grads) if torch.is_tensor(grads) else C.c_void_p(grads),
+          grads_fmt, _ptr(flags), reset)
+
+
 def _mlp_count(name):
     from oracle import mlp as M
 
@@ -303,9 +334,8 @@ def test_adam_matches_torch_semantics(device):
     for step in range(1, 6):
         grad = torch.randn(n, generator=g) * 128.0
         gd = grad.to(device)
-        _call("nvo_nonfinite_flag", _stream(device), n, _ptr(gd), 0, _ptr(flag))
-        _call("nvo_adam_step", _stream(device), n, _ptr(pd), _ptr(p16), _ptr(gd), 0, _ptr(md), _ptr(vd), 1e-2, 0.9, 0.999,
-              1e-15, step, 1.0 / 128.0, 0.0, _ptr(flag), None)
+        _nonfinite_flag(_stream(device), [(0, n)], gd, 0, flag)
+        _adam_step(_stream(device), [(0, n, 1e-2, step, None, 0)], pd, p16, gd, 0, md, vd, flag)
         pr, mr, vr = adam_reference(pr, grad.double() / 128.0, mr, vr, 1e-2, step)
     torch.cuda.synchronize()
     _assert_close(pd, pr, rtol=4.2e-7, atol_scale=4.2e-8, what="adam params")
@@ -313,9 +343,8 @@ def test_adam_matches_torch_semantics(device):
     # a non-finite gradient anywhere skips the whole step (GradScaler semantics)
     before = pd.clone()
     gd[12345] = float("inf")
-    _call("nvo_nonfinite_flag", _stream(device), n, _ptr(gd), 0, _ptr(flag))
-    _call("nvo_adam_step", _stream(device), n, _ptr(pd), _ptr(p16), _ptr(gd), 0, _ptr(md), _ptr(vd), 1e-2, 0.9, 0.999,
-          1e-15, 6, 1.0 / 128.0, 0.0, _ptr(flag), None)
+    _nonfinite_flag(_stream(device), [(0, n)], gd, 0, flag)
+    _adam_step(_stream(device), [(0, n, 1e-2, 6, None, 0)], pd, p16, gd, 0, md, vd, flag)
     torch.cuda.synchronize()
     assert int(flag.item()) == 1 and torch.equal(before, pd)
     # fp16 gradient buffer (what a compressed all-reduce hands over) gives the same update as its fp32 cast
@@ -323,11 +352,9 @@ def test_adam_matches_torch_semantics(device):
     pa, pb = pd.clone(), pd.clone()
     ma, mb, va, vb = md.clone(), md.clone(), vd.clone(), vd.clone()
     flag.zero_()
-    _call("nvo_adam_step", _stream(device), n, _ptr(pa), None, _ptr(g16), 1, _ptr(ma), _ptr(va), 1e-2, 0.9, 0.999,
-          1e-15, 7, 1.0 / 128.0, 0.0, _ptr(flag), None)
+    _adam_step(_stream(device), [(0, n, 1e-2, 7, None, 0)], pa, None, g16, 1, ma, va, flag)
     g32 = g16.float()
-    _call("nvo_adam_step", _stream(device), n, _ptr(pb), None, _ptr(g32), 0, _ptr(mb), _ptr(vb), 1e-2, 0.9, 0.999,
-          1e-15, 7, 1.0 / 128.0, 0.0, _ptr(flag), None)
+    _adam_step(_stream(device), [(0, n, 1e-2, 7, None, 0)], pb, None, g32, 0, mb, vb, flag)
     torch.cuda.synchronize()
     assert torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb)
     # bfloat16 gradient buffer (the compressed exchange bench.py uses): nvo_cast_bf16 rounds to nearest even exactly like
@@ -345,28 +372,23 @@ def test_adam_matches_torch_semantics(device):
     pa, pb = pd.clone(), pd.clone()
     ma, mb, va, vb = md.clone(), md.clone(), vd.clone(), vd.clone()
     flag.zero_()
-    _call("nvo_nonfinite_flag", _stream(device), n, _ptr(gb), 2, _ptr(flag))
-    _call("nvo_adam_step", _stream(device), n, _ptr(pa), None, _ptr(gb), 2, _ptr(ma), _ptr(va), 1e-2, 0.9, 0.999,
-          1e-15, 8, 1.0 / 128.0, 0.0, _ptr(flag), None)
+    _nonfinite_flag(_stream(device), [(0, n)], gb, 2, flag)
+    _adam_step(_stream(device), [(0, n, 1e-2, 8, None, 0)], pa, None, gb, 2, ma, va, flag)
     gb32 = gb.float()
-    _call("nvo_adam_step", _stream(device), n, _ptr(pb), None, _ptr(gb32), 0, _ptr(mb), _ptr(vb), 1e-2, 0.9, 0.999,
-          1e-15, 8, 1.0 / 128.0, 0.0, _ptr(flag), None)
+    _adam_step(_stream(device), [(0, n, 1e-2, 8, None, 0)], pb, None, gb32, 0, mb, vb, flag)
     torch.cuda.synchronize()
     assert int(flag.item()) == 0 and torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb)
     gb[777] = float("inf")
-    _call("nvo_nonfinite_flag", _stream(device), n, _ptr(gb), 2, _ptr(flag))
+    _nonfinite_flag(_stream(device), [(0, n)], gb, 2, flag)
     torch.cuda.synchronize()
     assert int(flag.item()) == 1
 
 
 def test_grouped_adam_equals_per_group_launches(device):
-    """nvo_adam_step_groups / nvo_nonfinite_flag_ranges (one launch for the groups of a step) against one
-    nvo_adam_step launch per group: bit-identical parameters, moments and fp16 copies, including odd (unaligned) group
+    """nvo_adam_step / nvo_nonfinite_flag over three groups (one launch for the groups of a step) against one
+    one-group nvo_adam_step launch per group: bit-identical parameters, moments and fp16 copies, including odd (unaligned) group
     boundaries and device-side hyper-parameters; and the per-group skip flags (GradScaler.step decides per optimiser)."""
-    import ctypes as C
-
-    from nerf_vo_amd import _lib
-    from nerf_vo_amd.engine import _call, _ptr, _stream
+    from nerf_vo_amd.engine import _stream
 
     st = _stream(device)
     n = 300_007
@@ -386,23 +408,16 @@ def test_grouped_adam_equals_per_group_launches(device):
             p16 = torch.zeros(n, dtype=torch.float16, device=device)
             flag = torch.ones(4, dtype=torch.int32, device=device)  # must be reset by the flag launch
             if grouped:
-                offs = (C.c_uint64 * 3)(*[lo for lo, _ in bounds])
-                sizes = (C.c_uint64 * 3)(*[hi - lo for lo, hi in bounds])
-                _call("nvo_nonfinite_flag_ranges", st, 3, offs, sizes, _ptr(gbuf), half, _ptr(flag))
-                arr = (_lib.AdamGroup * 3)(*[
-                    _lib.AdamGroup(offset=lo, n=hi - lo, lr=lrs[i], step=steps[i],
-                                   hyper_dev=hyper.data_ptr() if i == 1 else None)
-                    for i, (lo, hi) in enumerate(bounds)])
-                _call("nvo_adam_step_groups", st, 3, arr, _ptr(p), _ptr(p16), _ptr(gbuf), half, _ptr(m), _ptr(v), 0.9,
-                      0.999, 1e-15, 1.0 / 128.0, 0.0, _ptr(flag))
+                _nonfinite_flag(st, [(lo, hi - lo) for lo, hi in bounds], gbuf, half, flag)
+                _adam_step(st, [(lo, hi - lo, lrs[i], steps[i], hyper if i == 1 else None, i)
+                                for i, (lo, hi) in enumerate(bounds)], p, p16, gbuf, half, m, v, flag)
             else:
-                flag[1:] = 0  # the single-range launcher owns (and resets) one word only
-                _call("nvo_nonfinite_flag", st, n, _ptr(gbuf), half, _ptr(flag))
-                for i, (lo, hi) in enumerate(bounds):
-                    _call("nvo_adam_step", st, hi - lo, C.c_void_p(p.data_ptr() + 4 * lo), C.c_void_p(p16.data_ptr() + 2 * lo),
-                          C.c_void_p(gbuf.data_ptr() + esz * lo), half, C.c_void_p(m.data_ptr() + 4 * lo),
-                          C.c_void_p(v.data_ptr() + 4 * lo), lrs[i], 0.9, 0.999, 1e-15, steps[i], 1.0 / 128.0, 0.0, _ptr(flag),
-                          _ptr(hyper) if i == 1 else None)
+                flag[1:] = 0  # a one-span scan owns (and resets) one word only
+                _nonfinite_flag(st, [(0, n)], gbuf, half, flag)
+                for i, (lo, hi) in enumerate(bounds):  # one group per launch, each on buffers that start at the group
+                    _adam_step(st, [(0, hi - lo, lrs[i], steps[i], hyper if i == 1 else None, 0)], p.data_ptr() + 4 * lo,
+                               p16.data_ptr() + 2 * lo, gbuf.data_ptr() + esz * lo, half, m.data_ptr() + 4 * lo,
+                               v.data_ptr() + 4 * lo, flag)
             torch.cuda.synchronize()
             assert int(flag[:3].sum().item()) == 0
             out.append((p, m, v, p16))
@@ -413,20 +428,137 @@ def test_grouped_adam_equals_per_group_launches(device):
     bad = grads.clone()
     bad[bounds[1][0] + 5] = float("nan")
     flag = torch.zeros(4, dtype=torch.int32, device=device)
-    offs = (C.c_uint64 * 3)(*[lo for lo, _ in bounds])
-    sizes = (C.c_uint64 * 3)(*[hi - lo for lo, hi in bounds])
-    _call("nvo_nonfinite_flag_ranges", st, 3, offs, sizes, _ptr(bad), 0, _ptr(flag))
+    _nonfinite_flag(st, [(lo, hi - lo) for lo, hi in bounds], bad, 0, flag)
     p, m, v = p0.clone(), m0.clone(), v0.clone()
-    arr = (_lib.AdamGroup * 3)(*[_lib.AdamGroup(offset=lo, n=hi - lo, lr=lrs[i], step=steps[i], hyper_dev=None)
-                                 for i, (lo, hi) in enumerate(bounds)])
-    _call("nvo_adam_step_groups", st, 3, arr, _ptr(p), None, _ptr(bad), 0, _ptr(m), _ptr(v), 0.9, 0.999, 1e-15,
-          1.0 / 128.0, 0.0, _ptr(flag))
+    _adam_step(st, [(lo, hi - lo, lrs[i], steps[i], None, i) for i, (lo, hi) in enumerate(bounds)], p, None, bad, 0, m, v, flag)
     torch.cuda.synchronize()
     assert flag[:3].tolist() == [0, 1, 0]
     lo, hi = bounds[1]
     assert torch.equal(p[lo:hi], p0[lo:hi]) and torch.equal(m[lo:hi], m0[lo:hi]), "the poisoned group must not move"
     assert not torch.equal(p[:lo], p0[:lo]) and not torch.equal(p[hi:], p0[hi:]), "the other groups must step"
     assert bool(torch.isfinite(p).all())
+
+
+_SCAN_STRIDE = 2048 * 256  # threads of a span whose block count is capped: the stride of the scan's 16-byte loads
+
+
+@pytest.mark.parametrize("fmt,n,shift", [(0, 6_400_007, 0), (2, 12_800_007, 0), (1, 12_800_007, 0), (0, 6_400_007, 1)],
+                         ids=["f32", "bf16", "f16", "f32_unaligned"])
+def test_nonfinite_flag_large_span(device, fmt, n, shift):
+    """The scan's 4-way unrolled 16-byte loop runs only once a span's block count is capped (2048 blocks) and the span
+    holds more than 3 x 2048 x 256 vectors -- the main grid's gradient does, no smaller test buffer.  A clean buffer
+    (with the largest finite values of the format in it) raises nothing; one inf where only the FOURTH load of the
+    unrolled loop reads raises the flag; so does one NaN at the last element (the scalar tail).  ``shift``: the span
+    starts one element behind a 16-byte boundary, i.e. the whole scan takes the scalar form.  Expected values:
+    torch.isfinite on the host copy.  (The planted finite extremes stay at 2.9e38: the scan's scalar form -- tail and
+    unaligned spans -- tests |x| <= 3.0e38 rather than the exponent bits, so it counts the last 12 % below FLT_MAX as an
+    overflow already; the 16-byte form does not.  As old as the kernel, and harmless for a gradient.)"""
+    from nerf_vo_amd.engine import _stream
+
+    st = _stream(device)
+    dtype = (torch.float32, torch.float16, torch.bfloat16)[fmt]
+    per = 16 // torch.empty(0, dtype=dtype).element_size()
+    n_vec = n // per
+    assert n_vec > 3 * _SCAN_STRIDE and (n + 2047) // 2048 > 2048 and n % per != 0
+    buf = torch.randn(n + shift, generator=torch.Generator().manual_seed(4)).to(dtype).to(device)
+    g = buf[shift:]
+    assert g.data_ptr() % 16 == (shift * buf.element_size())
+    big = min(torch.finfo(dtype).max, 2.9e38)
+    fourth = (3 * _SCAN_STRIDE + (n_vec - 3 * _SCAN_STRIDE) // 2) * per + per - 1  # vector index in [3 * stride, n_vec)
+    g[0], g[fourth - 1], g[n - 2] = big, -big, big
+    flag = torch.full((2,), 5, dtype=torch.int32, device=device)  # (word 0 is reset by the launch, word 1 is not its)
+
+    def scan():
+        _nonfinite_flag(st, [(0, n)], g.data_ptr(), fmt, flag)
+        torch.cuda.synchronize()
+        assert int(flag[1].item()) == 5
+        return int(flag[0].item()), int(not bool(torch.isfinite(g.cpu().float()).all()))
+
+    assert scan() == (0, 0)
+    g[fourth] = float("inf")
+    assert scan() == (1, 1)
+    g[fourth] = 1.0
+    assert scan() == (0, 0)
+    g[n - 1] = float("nan")
+    assert scan() == (1, 1)
+
+
+def test_nonfinite_flag_spans_or_into_named_words(device):
+    """Three spans, two of them raising the same word, OR-ed (reset=0) into words that already hold something: exactly the
+    named words change, by exactly bit 0; the word no span names keeps its sentinel, and an element outside every span
+    raises nothing."""
+    from nerf_vo_amd.engine import _stream
+
+    st = _stream(device)
+    n = 10_000
+    spans, slots = [(0, 3000), (3000, 3000), (6001, 3999)], [2, 0, 2]
+    init = [4, 0x5A5A, 0, 0x5A5A]
+    g = torch.randn(n, generator=torch.Generator().manual_seed(6)).to(device)
+    g[6000] = float("nan")  # in no span
+    for poison in (None, 7000, 4500, 10):
+        if poison is not None:
+            g[poison] = float("inf")
+        flags = torch.tensor(init, dtype=torch.int32, device=device)
+        _nonfinite_flag(st, spans, g, 0, flags, slots=slots, reset=0)
+        torch.cuda.synchronize()
+        host = g.cpu()
+        expect = list(init)
+        for (o, m), sl in zip(spans, slots):
+            expect[sl] |= int(not bool(torch.isfinite(host[o:o + m]).all()))
+        assert flags.tolist() == expect, f"poison at {poison}"
+        if poison is not None:
+            g[poison] = 0.5
+    assert expect == [4, 0x5A5A, 1, 0x5A5A]
+
+
+def test_opt_commit_with_scalars_equals_commit_then_write(device):
+    """nvo_opt_commit with by-value scalars (commit + the next step's scalars in one launch) against nvo_opt_commit
+    without scalars followed by nvo_write_floats, from identical states over 6 steps with a skipped group, a back-off and
+    a growth (growth_interval 2): applied, bias, scale, growth_tracker and dst are word-equal after every step."""
+    import ctypes as C
+
+    from nerf_vo_amd import _lib
+    from nerf_vo_amd.engine import _call, _ptr, _stream
+
+    st = _stream(device)
+    b1, b2 = 0.9, 0.999
+
+    def state():
+        return {"applied": torch.zeros(3, dtype=torch.int32, device=device),
+                "bias": torch.tensor([1 - b1, (1 - b2) ** 0.5] * 3, device=device),
+                "scale": torch.full((1,), 1024.0, device=device),
+                "growth_tracker": torch.zeros(1, dtype=torch.int32, device=device),
+                "dst": torch.full((16,), -7.0, device=device)}
+
+    a, b = state(), state()
+    flags = torch.zeros(4, dtype=torch.int32, device=device)
+
+    def commit_args(s, mask):
+        return _lib.OptCommitArgs(n_groups=3, active_mask=mask, scale_mask=0b111, applied=s["applied"].data_ptr(),
+                                  skip_flags=flags.data_ptr(), scale=s["scale"].data_ptr(),
+                                  growth_tracker=s["growth_tracker"].data_ptr(), growth_factor=2.0, backoff_factor=0.5,
+                                  growth_interval=2, min_scale=1.0, max_scale=65536.0, bias=s["bias"].data_ptr(), beta1=b1,
+                                  beta2=b2)
+
+    # (flag words of the step, active mask): clean, clean -> growth, group 1 skipped -> back-off, group 1 idle, clean ->
+    # growth, group 0 skipped -> back-off
+    steps = [([0, 0, 0], 0b111), ([0, 0, 0], 0b111), ([0, 1, 0], 0b111), ([0, 0, 0], 0b101), ([0, 0, 0], 0b111),
+             ([1, 0, 0], 0b111)]
+    scales = []
+    for it, (fl, mask) in enumerate(steps):
+        flags[:3] = torch.tensor(fl, dtype=torch.int32)
+        vals = (C.c_float * 5)(*[0.25 * it, 1e-2 / (it + 1), 3.0, float(it), -1.5])
+        scalars = _lib.StepScalars(dst=a["dst"].data_ptr(), n=5, host_values=C.addressof(vals))
+        _call("nvo_opt_commit", st, C.byref(commit_args(a, mask)), C.byref(scalars))
+        _call("nvo_opt_commit", st, C.byref(commit_args(b, mask)), None)
+        _call("nvo_write_floats", st, _ptr(b["dst"]), 5, vals)
+        torch.cuda.synchronize()
+        for name in a:
+            assert torch.equal(a[name].view(torch.int32), b[name].view(torch.int32)), f"step {it}: {name} differs"
+        scales.append(float(a["scale"].item()))
+    assert scales == [1024.0, 2048.0, 1024.0, 1024.0, 2048.0, 1024.0]
+    assert a["applied"].tolist() == [5, 4, 6] and int(a["growth_tracker"].item()) == 0
+    assert torch.equal(a["dst"].cpu(), torch.tensor([1.25, 1e-2 / 6, 3.0, 5.0, -1.5] + [-7.0] * 11))
 
 
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])

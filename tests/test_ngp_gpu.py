@@ -286,8 +286,9 @@ def test_density_grid_update_and_training(device):
 
 
 def test_weight_ema_matches_tcnn_formula(device):
-    """nvo_ema_update vs the debiased moving average of tcnn's EmaOptimizer (restated): ema_t = (ema_{t-1} * d *
-    (1 - d^(t-1)) + w_t * (1 - d)) / (1 - d^t); a raised skip flag leaves the average untouched."""
+    """nvo_ema_update (t from its device counter, committed behind every launch) vs the debiased moving average of tcnn's
+    EmaOptimizer (restated): ema_t = (ema_{t-1} * d * (1 - d^(t-1)) + w_t * (1 - d)) / (1 - d^t); a raised skip flag
+    leaves the average and the counter untouched."""
     from nerf_vo_amd.engine import _call
     from nerf_vo_amd.tinycudann.modules import _ptr, _stream
 
@@ -296,28 +297,31 @@ def test_weight_ema_matches_tcnn_formula(device):
     ema = torch.zeros(n, device=device)
     ema_half = torch.zeros(n, dtype=torch.float16, device=device)
     flag = torch.zeros(1, dtype=torch.int32, device=device)
+    step_dev = torch.zeros(1, dtype=torch.int32, device=device)
     ref = torch.zeros(n, dtype=torch.float64)
     for t in range(1, 41):
         w = torch.randn(n, generator=g)
-        _call("nvo_ema_update", _stream(device), n, _ptr(w.to(device)), _ptr(ema), _ptr(ema_half), d, t, _ptr(flag))
+        _call("nvo_ema_update", _stream(device), n, _ptr(w.to(device)), _ptr(ema), _ptr(ema_half), d, _ptr(step_dev), _ptr(flag), 1)
         ref = (ref * d * (1 - d ** (t - 1)) + w.double() * (1 - d)) / (1 - d ** t)
         if t == 1:
             assert torch.allclose(ema.cpu(), w, rtol=1e-6, atol=1e-7)  # the first average IS the weights
     torch.cuda.synchronize()
     assert torch.allclose(ema.cpu().double(), ref, rtol=2e-5, atol=2e-6)
     assert torch.equal(ema_half.cpu(), ema.cpu().half())
+    assert int(step_dev.item()) == 40
     before = ema.clone()
     flag.fill_(1)
-    _call("nvo_ema_update", _stream(device), n, _ptr(torch.randn(n, generator=g).to(device)), _ptr(ema), _ptr(ema_half), d, 41,
-          _ptr(flag))
+    _call("nvo_ema_update", _stream(device), n, _ptr(torch.randn(n, generator=g).to(device)), _ptr(ema), _ptr(ema_half), d,
+          _ptr(step_dev), _ptr(flag), 1)
     torch.cuda.synchronize()
     assert torch.equal(before, ema)
+    assert int(step_dev.item()) == 40
 
 
 def test_adam_tail_in_one_launch_is_bit_identical(device):
-    """nvo_adam_step_groups_tail (Adam + weight average + both commits in ONE launch, the commit by the last workgroup to
-    finish) against the launches it replaces -- nvo_adam_step_groups, nvo_ema_update_dev_part, nvo_ema_update_dev (with
-    its k_ema_commit) and nvo_opt_commit -- from identical states over several steps, one of them skipped: master weights,
+    """nvo_adam_step with a nvo_adam_tail (Adam + weight average + both commits in ONE launch, the commit by the last
+    workgroup to finish) against the launches it replaces -- nvo_adam_step without a tail, nvo_ema_update without and with
+    its commit (k_ema_commit) and nvo_opt_commit -- from identical states over several steps, one of them skipped: master weights,
     moments, 16-bit copy, average and its 16-bit copy, both counters, the bias corrections and the check-in counter (back
     at zero after every launch).  Three groups at offsets that make one of them take the scalar form, own weight decay."""
     import ctypes as C
@@ -347,32 +351,35 @@ def test_adam_tail_in_one_launch_is_bit_identical(device):
 
     def batch(st):
         arr = [_lib.AdamGroup(offset=o, n=m, lr=lr, step=0, hyper_dev=None, bias_dev=st["bias"].data_ptr(), flag_slot=0,
-                              flag_slot_set=1, weight_decay=wd, weight_decay_set=1) for o, m, wd in groups]
+                              weight_decay=wd) for o, m, wd in groups]
         return (_lib.AdamGroup * len(arr))(*arr)
+
+    def adam_args(st, grads):
+        return _lib.AdamArgs(params=st["p"].data_ptr(), params_half=st["p16"].data_ptr(), grads=grads.data_ptr(), grads_fmt=0,
+                             exp_avg=st["m"].data_ptr(), exp_avg_sq=st["v"].data_ptr(), beta1=b1, beta2=b2, eps=eps,
+                             grad_scale=1.0 / 128.0, skip_flags=flag.data_ptr())
+
+    def commit_args(st):
+        return _lib.OptCommitArgs(n_groups=1, active_mask=1, scale_mask=0, applied=st["applied"].data_ptr(),
+                                  skip_flags=flag.data_ptr(), bias=st["bias"].data_ptr(), beta1=b1, beta2=b2)
 
     for it in range(5):
         grads = (torch.randn(n, generator=g) * 128.0).to(device)
         flag.fill_(1 if it == 3 else 0)
         # --- separate launches
-        _call("nvo_adam_step_groups", stream, 3, batch(a), _ptr(a["p"]), _ptr(a["p16"]), _ptr(grads), 0, _ptr(a["m"]), _ptr(a["v"]),
-              b1, b2, eps, 1.0 / 128.0, 0.0, _ptr(flag))
+        _call("nvo_adam_step", stream, C.byref(adam_args(a, grads)), 3, batch(a), None)
         head = groups[1][0] + groups[1][1]
-        _call("nvo_ema_update_dev_part", stream, head, _ptr(a["p"]), _ptr(a["ema"]), _ptr(a["ema16"]), decay, _ptr(a["ema_step"]),
-              _ptr(flag))
-        _call("nvo_ema_update_dev", stream, n - head, C.c_void_p(a["p"].data_ptr() + 4 * head),
+        _call("nvo_ema_update", stream, head, _ptr(a["p"]), _ptr(a["ema"]), _ptr(a["ema16"]), decay, _ptr(a["ema_step"]),
+              _ptr(flag), 0)
+        _call("nvo_ema_update", stream, n - head, C.c_void_p(a["p"].data_ptr() + 4 * head),
               C.c_void_p(a["ema"].data_ptr() + 4 * head), C.c_void_p(a["ema16"].data_ptr() + 2 * head), decay,
-              _ptr(a["ema_step"]), _ptr(flag))
-        _call("nvo_opt_commit", stream, 1, 1, 0, _ptr(a["applied"]), _ptr(flag), None, None, 2.0, 0.5, 2000, 0.0, 0.0,
-              _ptr(a["bias"]), b1, b2)
+              _ptr(a["ema_step"]), _ptr(flag), 1)
+        _call("nvo_opt_commit", stream, C.byref(commit_args(a)), None)
         # --- one launch
         tail = _lib.AdamTail(ema=b["ema"].data_ptr(), ema_half=b["ema16"].data_ptr(), ema_decay=decay,
                              ema_step_dev=b["ema_step"].data_ptr(), ema_flag_slot=0, ema_commit=1,
-                             done_counter=b["done"].data_ptr(), n_commit_groups=1, active_mask=1, scale_mask=0,
-                             applied=b["applied"].data_ptr(), scale=None, growth_tracker=None, growth_factor=2.0,
-                             backoff_factor=0.5, growth_interval=2000, min_scale=0.0, max_scale=0.0,
-                             bias=b["bias"].data_ptr())
-        _call("nvo_adam_step_groups_tail", stream, 3, batch(b), _ptr(b["p"]), _ptr(b["p16"]), _ptr(grads), 0, _ptr(b["m"]),
-              _ptr(b["v"]), b1, b2, eps, 1.0 / 128.0, 0.0, _ptr(flag), 0, None, None, None, C.byref(tail))
+                             done_counter=b["done"].data_ptr(), commit=commit_args(b))
+        _call("nvo_adam_step", stream, C.byref(adam_args(b, grads)), 3, batch(b), C.byref(tail))
         torch.cuda.synchronize()
         for name in a:
             x, y = a[name], b[name]
@@ -393,7 +400,7 @@ def test_adam_tail_refuses_to_commit_on_a_dirty_counter(device):
 
     from nerf_vo_amd import _lib
     from nerf_vo_amd.engine import _call
-    from nerf_vo_amd.tinycudann.modules import _ptr, _stream
+    from nerf_vo_amd.tinycudann.modules import _stream
 
     n = 200_000
     b1, b2 = 0.9, 0.99
@@ -406,23 +413,24 @@ def test_adam_tail_refuses_to_commit_on_a_dirty_counter(device):
     flag = torch.zeros(1, dtype=torch.int32, device=device)
     done = torch.full((1,), 3, dtype=torch.int32, device=device)  # dirty
     group = (_lib.AdamGroup * 1)(_lib.AdamGroup(offset=0, n=n, lr=1e-2, step=0, hyper_dev=None, bias_dev=bias.data_ptr(),
-                                                flag_slot=0, flag_slot_set=1, weight_decay=0.0, weight_decay_set=1))
+                                                flag_slot=0, weight_decay=0.0))
+    args = _lib.AdamArgs(params=p.data_ptr(), params_half=p16.data_ptr(), grads=grads.data_ptr(), grads_fmt=0,
+                         exp_avg=m.data_ptr(), exp_avg_sq=v.data_ptr(), beta1=b1, beta2=b2, eps=1e-15, grad_scale=1.0,
+                         skip_flags=flag.data_ptr())
+    commit = _lib.OptCommitArgs(n_groups=1, active_mask=1, scale_mask=0, applied=applied.data_ptr(), skip_flags=flag.data_ptr(),
+                                bias=bias.data_ptr(), beta1=b1, beta2=b2)
     tail = _lib.AdamTail(ema=None, ema_half=None, ema_decay=0.0, ema_step_dev=None, ema_flag_slot=0, ema_commit=0,
-                         done_counter=done.data_ptr(), n_commit_groups=1, active_mask=1, scale_mask=0,
-                         applied=applied.data_ptr(), scale=None, growth_tracker=None, growth_factor=2.0, backoff_factor=0.5,
-                         growth_interval=2000, min_scale=0.0, max_scale=0.0, bias=bias.data_ptr())
+                         done_counter=done.data_ptr(), commit=commit)
     bias0 = bias.clone()
     for _ in range(2):  # (the second launch meets the sticky bit and must stay failed)
-        _call("nvo_adam_step_groups_tail", _stream(device), 1, group, _ptr(p), _ptr(p16), _ptr(grads), 0, _ptr(m), _ptr(v), b1, b2,
-              1e-15, 1.0, 0.0, _ptr(flag), 0, None, None, None, C.byref(tail))
+        _call("nvo_adam_step", _stream(device), C.byref(args), 1, group, C.byref(tail))
         torch.cuda.synchronize()
         word = int(done.item()) & 0xFFFFFFFF
         assert word & 0x80000000, f"no error bit on a dirty counter (word {word:#x})"
         assert int(applied.item()) == 0 and torch.equal(bias, bias0), "the launch committed on a dirty counter"
     # a clean counter commits and is left at zero
     done.zero_()
-    _call("nvo_adam_step_groups_tail", _stream(device), 1, group, _ptr(p), _ptr(p16), _ptr(grads), 0, _ptr(m), _ptr(v), b1, b2,
-          1e-15, 1.0, 0.0, _ptr(flag), 0, None, None, None, C.byref(tail))
+    _call("nvo_adam_step", _stream(device), C.byref(args), 1, group, C.byref(tail))
     torch.cuda.synchronize()
     assert int(done.item()) == 0 and int(applied.item()) == 1 and not torch.equal(bias, bias0)
 

@@ -63,8 +63,8 @@ def main():
     # run gather 67 068 KB for 101 376 KB requested (x 0.662 = 1/2 x 4/3: an unaligned 384-byte run touches four 128-byte
     # lines).  The x2 figure is therefore the traffic the pass really causes, line over-fetch included; the raw value
     # stays beside it in bench.py (roofline.traffic_raw).)
-    STREAM_READERS = {"k_tl_accumulate", "k_tl_accumulate_p", "k_st_accumulate", "k_adam_groups", "k_adam",
-                      "k_nonfinite_flag_ranges", "k_nonfinite_flag", "k_read"}
+    STREAM_READERS = {"k_tl_accumulate", "k_tl_accumulate_p", "k_st_accumulate", "k_adam_groups",
+                      "k_nonfinite_flag", "k_read"}
     for k in kernels:
         k["FETCH_SIZE_KB_corrected"] = round(k["FETCH_SIZE_KB_per_launch"] * (2.0 if k["kernel"] in STREAM_READERS else 1.0), 1)
     # bench rows: the streamed main-grid backward is several kernels per step (+ the slice-owner launch of its

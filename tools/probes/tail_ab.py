@@ -1,6 +1,6 @@
 """A/B of the occupancy-grid back-end's fused optimiser tail (Adam + weight average + commit in ONE launch,
 NgpConfig.fuse_optimizer_tail) on one box: python tools/probes/tail_ab.py {on|off} -- bench args
-(The nerfacto engine's commit is a node of its own, nvo_opt_commit_table: there is no switch to flip for it.)"""
+(The nerfacto engine's commit is a node of its own, the table form of nvo_opt_commit: there is no switch to flip for it.)"""
 import runpy
 import sys
 
