@@ -1,10 +1,14 @@
+// The per-ray kernels as they stood BEFORE their loads were moved to the kernel entry (render.hip): verbatim copies,
+// kept for one change as the A/B and same-bits reference behind NVO_RAY_LEGACY=1 (tests/test_per_ray_forms_gpu.py,
+// EXPERIMENTS.md 12.4).  Not a product path; to be removed once the numbers are on record.  (k_weights_pdf_legacy is
+// also the form render.hip ships today: its entry-load form measured no faster and was not kept.)
 // Per-ray kernels of the mapping training step for gfx950, ONE WAVE (64 lanes) PER RAY:
-//   k_weights_pdf      density activation (trunc_exp) + volume-rendering weights + (optionally)
+//   k_weights_pdf_legacy      density activation (trunc_exp) + volume-rendering weights + (optionally)
 //                      histogram-CDF resampling of the next level's bins (PDFSampler)
-//   k_main_render_loss compositing (rgb with last-sample background, accumulation, median and
+//   k_main_render_loss_legacy compositing (rgb with last-sample background, accumulation, median and
 //                      expected depth) fused with the rgb / distortion / depth losses and their
 //                      gradients w.r.t. per-sample colour and density pre-activation
-//   k_prop_loss        interlevel (mip-NeRF 360 outer-measure) + depth loss of one proposal level and
+//   k_prop_loss_legacy        interlevel (mip-NeRF 360 outer-measure) + depth loss of one proposal level and
 //                      the gradient w.r.t. that level's density pre-activation
 // Prefix / suffix sums over a ray's samples are wavefront scans (shuffle network) with a carry
 // across 64-sample chunks; per-ray scratch lives in the wave's private LDS slice.
@@ -17,14 +21,12 @@
 #include "../../include/nerfvo_hip.h"
 
 #include <float.h>
-#include <stdlib.h>
 
 namespace {
 
 constexpr int kRayBlock = 256;          // 4 waves = 4 rays per workgroup
 constexpr int kRaysPerBlock = kRayBlock / 64;
 constexpr int kMaxS = 256;              // samples per ray handled by the LDS scratch
-constexpr int kChunks = kMaxS / 64;     // 64-sample chunks of the longest ray
 constexpr float kLossEps = 1.0e-7f;     // nerfstudio losses.EPS
 
 // (DPP forms, nvo_common.h: the shuffle forms were six dependent LDS round trips each)
@@ -96,75 +98,64 @@ __device__ __forceinline__ void ray_weights(int lane, uint32_t S, const nvo_h16*
     }
 }
 
-// ---- forward and backward one 64-sample chunk at a time, on operands the caller has loaded at the kernel entry -----
-// (k_main_render_loss, k_prop_loss)  A launch of these kernels is ONE round of waves (a ray each), so it lasts as long as
-// a ray's dependent chain: every global load of the ray is requested before the first wait and consumed later, and the
-// backward takes the selector, pre + bias and the interval length from the forward's registers instead of loading them
-// again.  The forward is ray_weights' arithmetic expression by expression (the library is built with -ffp-contract=off).
-// k_weights_pdf keeps the whole-ray form above: with its loads up front it measured no faster (EXPERIMENTS.md 12.4).
-// a lane's inputs of one chunk, requested at index min(base + lane, S - 1); pr stays in its 16-bit format until it is used
-// (a conversion next to the load waits for it, and the requests behind it would queue up after that wait)
-struct RayIn { float x0; nvo_h16 pr; float t0, t1; };
-__device__ __forceinline__ float h16_to_float(nvo_h16 raw, bool bf) {  // (nvo_ld16 without the load)
-    return bf ? __uint_as_float((uint32_t)raw << 16) : (float)__builtin_bit_cast(_Float16, raw);
-}
-__device__ __forceinline__ RayIn ray_fetch(int lane, uint32_t S, uint32_t base, const nvo_h16* __restrict__ pre, bool bf,
-                                           uint32_t pre_stride, const float* __restrict__ x01,
-                                           const float* __restrict__ tb) {
-    const uint32_t i = min(base + (uint32_t)lane, S - 1u);
-    RayIn v;
-    v.x0 = x01[3 * (size_t)i];
-    v.pr = pre[(size_t)i * pre_stride];
-    v.t0 = tb[i];
-    v.t1 = tb[i + 1];
-    return v;
-}
-// Everything requested above this line stays above it and nothing below it moves up: the loads of a kernel's entry are
-// not sunk to their first use (no instruction; the registers are not named, so nothing waits here).
-__device__ __forceinline__ void loads_issued() { asm volatile("" ::: "memory"); }
-
-struct RayKeep { bool sel; float x, delta; };  // what the backward needs again: selector, pre + bias, t[i+1] - t[i]
-// forward of one chunk; valid = the lane's sample exists (a lane without one holds the last sample's inputs: selected
-// away, never multiplied in).  w = 0 on such a lane.
-__device__ __forceinline__ void ray_weights_chunk(int lane, const RayIn& in, bool bf, bool valid, float bias, float& carry,
-                                                  float& w, float& T, RayKeep& k) {
-    k.sel = in.x0 > 0.f;
-    k.x = h16_to_float(in.pr, bf) + bias;
-    k.delta = in.t1 - in.t0;
-    float dd = 0.f, sg = 0.f;
-    if (valid) {
-        sg = k.sel ? __expf(fminf(k.x, 60.f)) : 0.f;  // (the cap: see ray_weights)
-        dd = k.delta * sg;
-    }
-    const float incl = wave_incl_scan(dd, lane) + carry;
-    T = __expf(-(incl - dd));
-    w = valid ? nan_to_num((1.f - __expf(-dd)) * T) : 0.f;
-    carry = nvo_wave_bcast(incl, 63);
-}
-// backward of one chunk: g = dL/dw of the lane's sample, total = sum over the ray of g_i w_i, carry = that sum over the
-// chunks before this one; returns dL/dpre * loss_scale in the 16-bit format it is stored in
+// dL/dw (in LDS array g[], overwritten) -> dL/dpre, written as fp16 * loss_scale
 // dL/dsigma_k = delta_k [ g_k (T_k - w_k) - sum_{i>k} g_i w_i ],  dsigma/dpre = exp(clamp(pre+bias,-15,15))
-// overflow (per lane, OR-ed in): a gradient of this ray does not survive that format
-__device__ __forceinline__ nvo_h16 ray_weights_bwd_chunk(int lane, bool valid, const RayKeep& k, float g, float w, float T,
-                                                         float total, float& carry, float loss_scale, bool bf,
-                                                         bool& overflow) {
+// returns (per lane): a gradient of this ray does not survive the 16-bit format it is stored in
+__device__ __forceinline__ bool ray_weights_bwd(int lane, uint32_t S, const nvo_h16* __restrict__ pre, bool bf,
+                                                uint32_t pre_stride, const float* __restrict__ x01,
+                                                const float* __restrict__ tb, float bias,
+                                                const float* w, const float* Tr, const float* g,
+                                                float loss_scale, nvo_h16* __restrict__ dpre,
+                                                uint32_t dpre_stride, bool zero_row = false,
+                                                unsigned long long* live = nullptr) {
+    // (live, S <= 64: lanes whose STORED 16-bit gradient is not zero)
+    bool overflow = false;
     const float fmt_max = bf ? 3.0e38f : 65504.0f;
-    const float gw = valid ? g * w : 0.f;
-    const float incl = wave_incl_scan(gw, lane) + carry;
-    float d = 0.f;
-    if (valid && k.sel) {
-        const float dsig = k.delta * (g * (T - w) - (total - incl));
-        d = dsig * __expf(fminf(fmaxf(k.x, -15.f), 15.f));
+    // total of g_i w_i, then inclusive prefix per chunk -> suffix (exclusive) = total - incl
+    float total = 0.f;
+    for (uint32_t base = 0; base < S; base += 64) {
+        const uint32_t i = base + lane;
+        total += (i < S) ? g[i] * w[i] : 0.f;
     }
-    if (valid) overflow = overflow || !(fabsf(d * loss_scale) <= fmt_max);
-    carry = nvo_wave_bcast(incl, 63);
-    return nvo_cvt16(d * loss_scale, bf);
+    total = wave_sum(total);
+    float carry = 0.f;
+    for (uint32_t base = 0; base < S; base += 64) {
+        const uint32_t i = base + lane;
+        const float gw = (i < S) ? g[i] * w[i] : 0.f;
+        const float incl = wave_incl_scan(gw, lane) + carry;
+        if (i < S) {
+            const bool sel = x01[3 * (size_t)i] > 0.f;
+            float d = 0.f;
+            if (sel) {
+                const float x = nvo_ld16(pre + (size_t)i * pre_stride, bf) + bias;
+                const float delta = tb[i + 1] - tb[i];
+                const float dsig = delta * (g[i] * (Tr[i] - w[i]) - (total - incl));
+                d = dsig * __expf(fminf(fmaxf(x, -15.f), 15.f));
+            }
+            overflow = overflow || !(fabsf(d * loss_scale) <= fmt_max);
+            const nvo_h16 d16 = nvo_cvt16(d * loss_scale, bf);
+            if (live) *live = __ballot((d16 & 0x7fffu) != 0u);
+            if (zero_row && dpre_stride == 16) {
+                // whole 32-byte row {d, 0 x 15} as two 16-byte stores (the MLP backward reads all 16 columns)
+                uint4 lo = make_uint4(0u, 0u, 0u, 0u);
+                lo.x = (uint32_t)d16;
+                uint4* row = reinterpret_cast<uint4*>(dpre + (size_t)i * 16);
+                row[0] = lo;
+                row[1] = make_uint4(0u, 0u, 0u, 0u);
+            } else {
+                dpre[(size_t)i * dpre_stride] = d16;
+            }
+        }
+        carry = nvo_wave_bcast(incl, 63);
+    }
+    return overflow;
 }
+
 // ------------------------------------------------------------------------------------------------
 // weights (+ PDF resampling)
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kRayBlock)
-k_weights_pdf(nvo_weights_pdf_args a) {
+k_weights_pdf_legacy(nvo_weights_pdf_args a) {
     __shared__ float lds[kRaysPerBlock][3][kMaxS + 4];
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
     const uint32_t r = blockIdx.x * kRaysPerBlock + wib;
@@ -243,13 +234,16 @@ k_weights_pdf(nvo_weights_pdf_args a) {
 // main level: render + losses + gradients
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kRayBlock)
-k_main_render_loss(nvo_main_loss_args a) {
-    __shared__ float lds[kRaysPerBlock][2][64 + 4];
+k_main_render_loss_legacy(nvo_main_loss_args a) {
+    __shared__ float lds[kRaysPerBlock][4][64 + 4];
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
     const uint32_t r = blockIdx.x * kRaysPerBlock + wib;
     if (r >= a.R) return;
-    float* w = lds[wib][0];   // (read at other lanes' indices by the distortion term only)
-    float* ut = lds[wib][1];
+    if (a.loss_scale_dev) a.loss_scale = *a.loss_scale_dev;  // dynamic loss scale (GradScaler state on the device)
+    float* w = lds[wib][0];
+    float* Tr = lds[wib][1];
+    float* g = lds[wib][2];
+    float* ut = lds[wib][3];
     const uint32_t S = a.S;
     const size_t so = (size_t)r * S;
     const float* tb = a.tbins + (size_t)r * (S + 1);
@@ -257,49 +251,16 @@ k_main_render_loss(nvo_main_loss_args a) {
     const nvo_h16* pre = (const nvo_h16*)a.pre + so * a.pre_stride;
     const bool bf = a.act_bf16 != 0;
     const float* x01 = a.x01 + 3 * so;
+    ray_weights(lane, S, pre, bf, a.pre_stride, x01, tb, a.density_bias, nullptr, w, Tr);
     const bool act = (uint32_t)lane < S;
-    const uint32_t li = min((uint32_t)lane, S - 1u);  // the index every lane loads at: its own sample, or the last one
-    // what this call computes (all uniform: tests of arguments); the inference call loads nothing that only training reads
-    const bool train = a.dpre != nullptr;
-    const bool has_normals = a.dsigma_dx != nullptr;
-    const bool use_dist = train && a.distortion_mult != 0.f;
-    const bool use_depth = train && a.depth_mult != 0.f && a.gt_depth;
-    const bool use_gt_normal = train && has_normals && a.gt_normal && a.normal_mult != 0.f;
-    // ---- every global load of the ray, before the first wait
-    const RayIn in = ray_fetch(lane, S, 0, pre, bf, a.pre_stride, x01, tb);
-    const nvo_h16* cp = (const nvo_h16*)a.rgb + (so + li) * a.rgb_stride;
-    const nvo_h16 c16[3] = {cp[0], cp[1], cp[2]};
-    float s0 = 0.f, s1 = 0.f;
-    if (use_dist) { s0 = sb[li]; s1 = sb[li + 1]; }
-    float gd[3] = {0.f, 0.f, 0.f};
-    if (has_normals) {
-        const float* gp = a.dsigma_dx + 3 * (so + li);
-        gd[0] = gp[0]; gd[1] = gp[1]; gd[2] = gp[2];
-    }
-    float gt[3] = {0.f, 0.f, 0.f}, gtn[3] = {0.f, 0.f, 0.f};
-    float gt_z = 0.f, dir_norm = 0.f;
-    if (train) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) gt[k] = a.gt_rgb[3 * (size_t)r + k];
-        if (use_depth) { gt_z = a.gt_depth[r]; dir_norm = a.directions_norm[r]; }
-        if (use_gt_normal) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) gtn[k] = a.gt_normal[3 * (size_t)r + k];
-        }
-        if (a.loss_scale_dev) a.loss_scale = *a.loss_scale_dev;  // dynamic loss scale (GradScaler state on the device)
-    }
-    loads_issued();
-
-    float carry = 0.f, wi, Ti;
-    RayKeep keep;
-    ray_weights_chunk(lane, in, bf, act, a.density_bias, carry, wi, Ti, keep);
-    if (use_dist && act) w[lane] = wi;
+    const float wi = act ? w[lane] : 0.f;
     if (a.weights && act) a.weights[so + lane] = wi;
 
     // ---- composite
     float c[3] = {0.f, 0.f, 0.f};
     if (act) {
-        c[0] = h16_to_float(c16[0], bf); c[1] = h16_to_float(c16[1], bf); c[2] = h16_to_float(c16[2], bf);
+        const nvo_h16* cp = (const nvo_h16*)a.rgb + (so + lane) * a.rgb_stride;
+        c[0] = nvo_ld16(cp, bf); c[1] = nvo_ld16(cp + 1, bf); c[2] = nvo_ld16(cp + 2, bf);
     }
     const float acc = wave_sum(wi);
     float pix[3], clast[3];
@@ -308,7 +269,7 @@ k_main_render_loss(nvo_main_loss_args a) {
         clast[k] = nvo_wave_bcast(c[k], (int)S - 1);
         pix[k] = wave_sum(wi * c[k]) + clast[k] * (1.f - acc);
     }
-    const float mid = act ? 0.5f * (in.t0 + in.t1) : 0.f;
+    const float mid = act ? 0.5f * (tb[lane] + tb[lane + 1]) : 0.f;
     // median depth: first sample whose cumulative weight reaches 0.5 (clamped to the last sample)
     const float cum = wave_incl_scan(wi, lane);
     const unsigned long long ballot = __ballot(act && cum >= 0.5f);
@@ -330,10 +291,12 @@ k_main_render_loss(nvo_main_loss_args a) {
     float nrm[3] = {0.f, 0.f, 0.f};
     float Nv[3] = {0.f, 0.f, 0.f}, Nhat[3] = {0.f, 0.f, 0.f};
     float rN = 0.f;
+    const bool has_normals = a.dsigma_dx != nullptr;
     if (has_normals) {
         if (act) {
-            const float gx = gd[0] * a.dsigma_inv_scale, gy = gd[1] * a.dsigma_inv_scale,
-                        gz = gd[2] * a.dsigma_inv_scale;
+            const float* gp = a.dsigma_dx + 3 * (so + lane);
+            const float gx = gp[0] * a.dsigma_inv_scale, gy = gp[1] * a.dsigma_inv_scale,
+                        gz = gp[2] * a.dsigma_inv_scale;
             const float inv = -1.f / fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-12f);  // F.normalize eps
             nrm[0] = gx * inv; nrm[1] = gy * inv; nrm[2] = gz * inv;
         }
@@ -354,7 +317,7 @@ k_main_render_loss(nvo_main_loss_args a) {
     float l_rgb = 0.f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float e = pix[k] - gt[k];
+        const float e = pix[k] - a.gt_rgb[3 * (size_t)r + k];
         l_rgb += e * e;
         dpix[k] = a.rgb_mult * 2.f * e * a.inv_rays * (1.f / 3.f);
     }
@@ -376,7 +339,7 @@ k_main_render_loss(nvo_main_loss_args a) {
     // distortion (spacing domain): sum_i w_i sum_j w_j |ut_i-ut_j| + sum_i w_i^2 (s_{i+1}-s_i)/3
     float l_dist = 0.f;
     if (a.distortion_mult != 0.f) {
-        const float uti = act ? 0.5f * (s0 + s1) : 0.f;
+        const float uti = act ? 0.5f * (sb[lane] + sb[lane + 1]) : 0.f;
         if (act) ut[lane] = uti;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -385,18 +348,18 @@ k_main_render_loss(nvo_main_loss_args a) {
         if (act) {
             for (uint32_t j = 0; j < S; ++j) inner += w[j] * fabsf(uti - ut[j]);
         }
-        const float ds = act ? (s1 - s0) : 0.f;
+        const float ds = act ? (sb[lane + 1] - sb[lane]) : 0.f;
         l_dist = wave_sum(wi * inner + wi * wi * ds * (1.f / 3.f)) * a.inv_rays;
         if (act) gw += a.distortion_mult * a.inv_rays * (2.f * inner + 2.f * wi * ds * (1.f / 3.f));
     }
     // DS-NeRF depth loss on this level
     float l_depth = 0.f;
-    if (use_depth) {
-        const float z = gt_z * dir_norm;
+    if (a.depth_mult != 0.f && a.gt_depth) {
+        const float z = a.gt_depth[r] * a.directions_norm[r];
         const float mask = z > 0.f ? 1.f : 0.f;
         float term = 0.f;
         if (act) {
-            const float len = in.t1 - in.t0;
+            const float len = tb[lane + 1] - tb[lane];
             const float gss = __expf(-((mid - z) * (mid - z)) / (2.f * a.depth_sigma)) * len * mask;
             term = -__logf(wi + kLossEps) * gss;
             gw += a.depth_mult * a.depth_level_div * a.inv_rays * (-gss / (wi + kLossEps));
@@ -405,13 +368,13 @@ k_main_render_loss(nvo_main_loss_args a) {
     }
     // monosdf normal loss on the shaded normals: L1 + (1 - cos) between the L2-normalised vectors
     float l_normal = 0.f;
-    if (use_gt_normal) {
+    if (has_normals && a.gt_normal && a.normal_mult != 0.f) {
         float sh[3], q[3], p[3], dp[3];
         float rs = 0.f, rq = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             sh[k] = 0.5f * (Nhat[k] + 1.f);
-            q[k] = gtn[k];
+            q[k] = a.gt_normal[3 * (size_t)r + k];
             rs += sh[k] * sh[k];
             rq += q[k] * q[k];
         }
@@ -456,16 +419,13 @@ k_main_render_loss(nvo_main_loss_args a) {
         atomicAdd(shard + 2, a.depth_mult * l_depth);
         if (l_normal != 0.f) atomicAdd(shard + 6, a.normal_mult * l_normal);
     }
-    // ---- dL/dw -> dL/dpre (one chunk: the lane's own gw, wi, Ti; nothing is loaded again)
-    float total = 0.f;
-    total += act ? gw * wi : 0.f;
-    total = wave_sum(total);
-    bool overflow = false;
-    carry = 0.f;
-    const nvo_h16 dpre16 = ray_weights_bwd_chunk(lane, act, keep, gw, wi, Ti, total, carry, a.loss_scale, bf, overflow);
-    if (act) ((nvo_h16*)a.dpre)[(so + lane) * a.dpre_stride] = dpre16;
-    // lanes whose STORED 16-bit gradient is not zero
-    const unsigned long long pre_live = __ballot(act && (dpre16 & 0x7fffu) != 0u);
+    if (act) g[lane] = gw;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    unsigned long long pre_live = 0ull;
+    bool overflow = ray_weights_bwd(lane, S, pre, bf, a.pre_stride, x01, tb, a.density_bias, w, Tr, g, a.loss_scale,
+                                    (nvo_h16*)a.dpre + so * a.dpre_stride, a.dpre_stride, false, &pre_live);
     if (act) {
         const float fmt_max = bf ? 3.0e38f : 65504.0f;
 #pragma unroll
@@ -512,78 +472,44 @@ k_main_render_loss(nvo_main_loss_args a) {
 // Workgroups [0, blocks0) serve a0, the rest a1: both proposal levels of a step in ONE launch (nvo_prop_loss_pair) --
 // each level alone is a single round of 4096 waves that lasts as long as one ray's dependent chain (17-22 us), so two
 // launches cost two chains.
-// The paired launch of a 4096-ray step is 8192 waves = the chip's 32 waves per CU: at most 64 VGPRs and 20 KiB of LDS per
-// workgroup keep 8 workgroups on a CU and the whole launch resident in ONE round (with 28 waves per CU an eighth of it
-// ran as a second round behind a full chain).  w, pre + bias, the interval and its mid-point are only ever read at the
-// lane's own samples: registers, one per chunk; g, cy, sb are read at other indices (LDS), and Tr takes the fourth row.
-__global__ void __launch_bounds__(kRayBlock) __attribute__((amdgpu_waves_per_eu(8)))
-k_prop_loss(nvo_prop_loss_args a0, nvo_prop_loss_args a1, uint32_t blocks0) {
-    __shared__ float lds[kRaysPerBlock][4][kMaxS + 4];
+__global__ void __launch_bounds__(kRayBlock)
+k_prop_loss_legacy(nvo_prop_loss_args a0, nvo_prop_loss_args a1, uint32_t blocks0) {
+    __shared__ float lds[kRaysPerBlock][5][kMaxS + 4];
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
     const bool second = blockIdx.x >= blocks0;  // (uniform)
     nvo_prop_loss_args a = second ? a1 : a0;
     const uint32_t r = (second ? blockIdx.x - blocks0 : blockIdx.x) * kRaysPerBlock + wib;
     if (r >= a.R) return;
-    float* Tr = lds[wib][0];
-    float* g = lds[wib][1];     // dL/dw of this level (built through a difference array)
-    float* cy = lds[wib][2];    // exclusive cumsum of w: cy[0] = 0, cy[j+1] = sum_{<=j} w
-    // the two binary searches per main interval walk this level's spacing bins: staged in LDS, each probe
-    // is an LDS read instead of a dependent global load
-    float* sb = lds[wib][3];
+    if (a.loss_scale_dev) a.loss_scale = *a.loss_scale_dev;
+    float* w = lds[wib][0];
+    float* Tr = lds[wib][1];
+    float* g = lds[wib][2];     // dL/dw of this level (built through a difference array)
+    float* cy = lds[wib][3];    // exclusive cumsum of w: cy[0] = 0, cy[j+1] = sum_{<=j} w
     const uint32_t S = a.S, Sm = a.S_main;
     const size_t so = (size_t)r * S;
     const float* tb = a.tbins + (size_t)r * (S + 1);
+    // the two binary searches per main interval walk this level's spacing bins: staged in LDS, each probe
+    // is an LDS read instead of a dependent global load
+    float* sb = lds[wib][4];
+    {
+        const float* sbg = a.sbins + (size_t)r * (S + 1);
+        for (uint32_t i = lane; i < S + 1; i += 64) sb[i] = sbg[i];
+    }
     const nvo_h16* pre = (const nvo_h16*)a.pre + so * a.pre_stride;
     const bool bf = a.act_bf16 != 0;
     const float* x01 = a.x01 + 3 * so;
-    const bool use_depth = a.depth_mult != 0.f && a.gt_depth;
-    // ---- every global load of the ray, before the first wait.  No test of S around them: a chunk past the ray's end asks for
-    // the last sample again (one line, the same for all lanes) -- behind a branch the selector's compare is folded into
-    // the branch's join and each chunk waits for its own loads before the next chunk's are requested
-    RayIn in[kChunks];
-    float sbv[kChunks + 1];
-    {
-        const float* sbg = a.sbins + (size_t)r * (S + 1);
-#pragma unroll
-        for (int c = 0; c < kChunks; ++c) in[c] = ray_fetch(lane, S, (uint32_t)c * 64u, pre, bf, a.pre_stride, x01, tb);
-#pragma unroll
-        for (int c = 0; c <= kChunks; ++c) sbv[c] = sbg[min((uint32_t)c * 64u + (uint32_t)lane, S)];
-    }
-    const uint32_t lm = min((uint32_t)lane, Sm - 1u);  // the lane's main-level interval, or the last one
-    const float* cm = a.sbins_main + (size_t)r * (Sm + 1);
-    const float cm0 = cm[lm], cm1 = cm[lm + 1];
-    const float wm = a.weights_main[(size_t)r * Sm + lm];
-    float gt_z = 0.f, dir_norm = 0.f;
-    if (use_depth) { gt_z = a.gt_depth[r]; dir_norm = a.directions_norm[r]; }
-    if (a.dpre && a.loss_scale_dev) a.loss_scale = *a.loss_scale_dev;
-    loads_issued();
+    ray_weights(lane, S, pre, bf, a.pre_stride, x01, tb, a.density_bias, nullptr, w, Tr);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-#pragma unroll
-    for (int c = 0; c <= kChunks; ++c) {
-        const uint32_t i = (uint32_t)c * 64u + (uint32_t)lane;
-        if (i < S + 1u) sb[i] = sbv[c];
-    }
-    // ---- weights and their exclusive prefix sum, chunk by chunk with the carries of ray_weights
-    float wv[kChunks], xk[kChunks], t0[kChunks], t1[kChunks];
-    uint32_t selm = 0u;  // bit c: the selector of the lane's sample of chunk c
-    {
-        float carry = 0.f, carry_cy = 0.f;
-#pragma unroll
-        for (int c = 0; c < kChunks; ++c) {
-            wv[c] = 0.f; xk[c] = 0.f; t0[c] = in[c].t0; t1[c] = in[c].t1;
-            if ((uint32_t)c * 64u < S) {
-                const uint32_t i = (uint32_t)c * 64u + (uint32_t)lane;
-                float T;
-                RayKeep k;
-                ray_weights_chunk(lane, in[c], bf, i < S, a.density_bias, carry, wv[c], T, k);
-                if (i < S) Tr[i] = T;
-                xk[c] = k.x;
-                selm |= k.sel ? (1u << c) : 0u;
-                const float incl = wave_incl_scan(wv[c], lane) + carry_cy;
-                if (i < S) cy[i + 1] = incl;
-                carry_cy = nvo_wave_bcast(incl, 63);
-            }
-        }
+    float carry = 0.f;
+    for (uint32_t base = 0; base < S; base += 64) {
+        const uint32_t i = base + lane;
+        const float v = (i < S) ? w[i] : 0.f;
+        const float incl = wave_incl_scan(v, lane) + carry;
+        if (i < S) cy[i + 1] = incl;
+        carry = nvo_wave_bcast(incl, 63);
     }
     if (lane == 0) cy[0] = 0.f;
     for (uint32_t i = lane; i < S + 2; i += 64) g[i] = 0.f;
@@ -594,9 +520,11 @@ k_prop_loss(nvo_prop_loss_args a0, nvo_prop_loss_args a1, uint32_t blocks0) {
     // ---- interlevel: one main-level interval per lane
     float l_inter = 0.f;
     if ((uint32_t)lane < Sm) {
-        int lo = upper_bound(sb, (int)S, cm0) - 1;          // over interval starts sb[0..S)
+        const float* cm = a.sbins_main + (size_t)r * (Sm + 1);
+        const float wm = a.weights_main[(size_t)r * Sm + lane];
+        int lo = upper_bound(sb, (int)S, cm[lane]) - 1;          // over interval starts sb[0..S)
         lo = min(max(lo, 0), (int)S - 1);
-        int hi = upper_bound(sb + 1, (int)S, cm1);          // over interval ends sb[1..S]
+        int hi = upper_bound(sb + 1, (int)S, cm[lane + 1]);      // over interval ends sb[1..S]
         hi = min(max(hi, 0), (int)S - 1);
         const float w_outer = cy[hi + 1] - cy[lo];
         const float diff = wm - w_outer;
@@ -614,29 +542,25 @@ k_prop_loss(nvo_prop_loss_args a0, nvo_prop_loss_args a1, uint32_t blocks0) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     // difference array -> dL/dw_j (inclusive prefix), plus the depth term
     float l_depth = 0.f;
-    const float z = use_depth ? gt_z * dir_norm : 0.f;
+    const bool use_depth = a.depth_mult != 0.f && a.gt_depth;
+    const float z = use_depth ? a.gt_depth[r] * a.directions_norm[r] : 0.f;
     const float mask = z > 0.f ? 1.f : 0.f;
-    {
-        float carry = 0.f;
-#pragma unroll
-        for (int c = 0; c < kChunks; ++c) {
-            if ((uint32_t)c * 64u < S) {
-                const uint32_t i = (uint32_t)c * 64u + (uint32_t)lane;
-                const float v = (i < S) ? g[i] : 0.f;
-                const float incl = wave_incl_scan(v, lane) + carry;
-                carry = nvo_wave_bcast(incl, 63);
-                float gi = incl;
-                if (i < S && use_depth) {
-                    const float midp = 0.5f * (t0[c] + t1[c]);
-                    const float len = t1[c] - t0[c];
-                    const float gss = __expf(-((midp - z) * (midp - z)) / (2.f * a.depth_sigma)) * len * mask;
-                    l_depth += -__logf(wv[c] + kLossEps) * gss;
-                    gi += a.depth_mult * a.depth_level_div * a.inv_rays * (-gss / (wv[c] + kLossEps));
-                }
-                // all lanes finished reading g[i] of this chunk through the scan before it is overwritten
-                if (i < S) g[i] = gi;
-            }
+    carry = 0.f;
+    for (uint32_t base = 0; base < S; base += 64) {
+        const uint32_t i = base + lane;
+        const float v = (i < S) ? g[i] : 0.f;
+        const float incl = wave_incl_scan(v, lane) + carry;
+        carry = nvo_wave_bcast(incl, 63);
+        float gi = incl;
+        if (i < S && use_depth) {
+            const float midp = 0.5f * (tb[i] + tb[i + 1]);
+            const float len = tb[i + 1] - tb[i];
+            const float gss = __expf(-((midp - z) * (midp - z)) / (2.f * a.depth_sigma)) * len * mask;
+            l_depth += -__logf(w[i] + kLossEps) * gss;
+            gi += a.depth_mult * a.depth_level_div * a.inv_rays * (-gss / (w[i] + kLossEps));
         }
+        // all lanes finished reading g[i] of this chunk through the scan before it is overwritten
+        if (i < S) g[i] = gi;
     }
     l_depth = wave_sum(l_depth) * a.inv_rays * a.depth_level_div;
     if (lane == 0) {
@@ -650,44 +574,8 @@ k_prop_loss(nvo_prop_loss_args a0, nvo_prop_loss_args a1, uint32_t blocks0) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // ---- dL/dw -> dL/dpre: total of g_i w_i, then per chunk the inclusive prefix -> suffix (exclusive) = total - incl
-    float total = 0.f;
-#pragma unroll
-    for (int c = 0; c < kChunks; ++c) {
-        const uint32_t i = (uint32_t)c * 64u + (uint32_t)lane;
-        if ((uint32_t)c * 64u < S) total += (i < S) ? g[i] * wv[c] : 0.f;
-    }
-    total = wave_sum(total);
-    bool overflow = false;
-    {
-        float carry = 0.f;
-        nvo_h16* dpre = (nvo_h16*)a.dpre + so * a.dpre_stride;
-#pragma unroll
-        for (int c = 0; c < kChunks; ++c) {
-            if ((uint32_t)c * 64u < S) {
-                const uint32_t i = (uint32_t)c * 64u + (uint32_t)lane;
-                const bool valid = i < S;
-                RayKeep k;
-                k.sel = ((selm >> c) & 1u) != 0u;
-                k.x = xk[c];
-                k.delta = t1[c] - t0[c];
-                const float gi = valid ? g[i] : 0.f, Ti = valid ? Tr[i] : 0.f;
-                const nvo_h16 d16 = ray_weights_bwd_chunk(lane, valid, k, gi, wv[c], Ti, total, carry, a.loss_scale, bf, overflow);
-                if (valid) {
-                    if (a.dpre_stride == 16) {
-                        // whole 32-byte row {d, 0 x 15} as two 16-byte stores (the MLP backward reads all 16 columns)
-                        uint4 lo = make_uint4(0u, 0u, 0u, 0u);
-                        lo.x = (uint32_t)d16;
-                        uint4* row = reinterpret_cast<uint4*>(dpre + (size_t)i * 16);
-                        row[0] = lo;
-                        row[1] = make_uint4(0u, 0u, 0u, 0u);
-                    } else {
-                        dpre[(size_t)i * a.dpre_stride] = d16;
-                    }
-                }
-            }
-        }
-    }
+    const bool overflow = ray_weights_bwd(lane, S, pre, bf, a.pre_stride, x01, tb, a.density_bias, w, Tr, g, a.loss_scale,
+                                          (nvo_h16*)a.dpre + so * a.dpre_stride, a.dpre_stride, true);
     if (a.nonfinite_flag && __ballot(overflow) != 0ull && lane == 0) atomicOr(a.nonfinite_flag, 1u);
     if (a.dpre_stride != 16) {
         for (uint32_t i = lane; i < S; i += 64) {
@@ -700,82 +588,18 @@ k_prop_loss(nvo_prop_loss_args a0, nvo_prop_loss_args a1, uint32_t blocks0) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
-// exported entry points (group C of include/nerfvo_hip.h)
+// launch functions for the launchers of render.hip (which have checked the arguments)
 // ---------------------------------------------------------------------------------------------
-// NVO_RAY_LEGACY=1 (tests and A/B; read per launch -- a captured graph keeps what it was captured with): the kernels
-// of render_legacy.hip instead
-static bool ray_legacy() {
-    const char* const e = getenv("NVO_RAY_LEGACY");
-    return e && e[0] == '1';
+void nvo_ray_legacy_weights_pdf(hipStream_t stream, const nvo_weights_pdf_args& a) {
+    NVO_LAUNCH(k_weights_pdf_legacy, dim3(nvo_div_up(a.R, kRaysPerBlock)), dim3(kRayBlock), 0, stream, a);
 }
 
-extern "C" {
-
-int nvo_weights_pdf(nvo_stream_t stream, const nvo_weights_pdf_args* args) {
-    NVO_REQUIRE(args != nullptr, "weights_pdf: args is NULL");
-    const nvo_weights_pdf_args a = *args;
-    NVO_REQUIRE(a.S >= 1 && a.S <= (uint32_t)kMaxS, "weights_pdf: samples per ray %u not in 1..%d", a.S, kMaxS);
-    NVO_REQUIRE(a.S_out <= (uint32_t)kMaxS, "weights_pdf: S_out %u > %d", a.S_out, kMaxS);
-    NVO_REQUIRE(a.S_out == 0 || (a.sbins_out && a.tbins_out), "weights_pdf: output bins are NULL");
-    NVO_REQUIRE(a.pre && a.x01 && a.tbins && a.weights && a.sbins, "weights_pdf: NULL input");
-    NVO_REQUIRE(!a.x01_out || (a.origins && a.directions && a.S_out > 0), "weights_pdf: x01_out needs origins, directions and S_out");
-    if (a.R == 0) return NVO_OK;
-    NVO_PROF(stream, "weights_pdf[S%u]", a.S);
-    if (ray_legacy()) nvo_ray_legacy_weights_pdf((hipStream_t)stream, a);
-    else NVO_LAUNCH(k_weights_pdf, dim3(nvo_div_up(a.R, kRaysPerBlock)), dim3(kRayBlock), 0, (hipStream_t)stream, a);
-    NVO_CHECK_LAUNCH();
-    return NVO_OK;
+void nvo_ray_legacy_main_render_loss(hipStream_t stream, const nvo_main_loss_args& a) {
+    NVO_LAUNCH(k_main_render_loss_legacy, dim3(nvo_div_up(a.R, kRaysPerBlock)), dim3(kRayBlock), 0, stream, a);
 }
 
-int nvo_main_render_loss(nvo_stream_t stream, const nvo_main_loss_args* args) {
-    NVO_REQUIRE(args != nullptr, "main_render_loss: args is NULL");
-    const nvo_main_loss_args a = *args;
-    NVO_REQUIRE(a.S >= 1 && a.S <= 64, "main_render_loss: samples per ray %u not in 1..64", a.S);
-    NVO_REQUIRE(a.pre && a.rgb && a.x01 && a.sbins && a.tbins && a.out_rgb && a.out_depth &&
-                a.out_accumulation, "main_render_loss: NULL input/output");
-    NVO_REQUIRE(!a.dpre || (a.drgb && a.losses && a.gt_rgb && a.drgb_stride >= 3),
-                "main_render_loss: training mode needs drgb, losses, gt_rgb");
-    NVO_REQUIRE(!a.tile_live || (a.dpre && (a.S & 15u) == 0u), "main_render_loss: tile_live needs training mode and S %% 16 == 0 (S = %u)", a.S);
-    if (a.R == 0) return NVO_OK;
-    NVO_PROF(stream, "main_render_loss");
-    if (ray_legacy()) nvo_ray_legacy_main_render_loss((hipStream_t)stream, a);
-    else NVO_LAUNCH(k_main_render_loss, dim3(nvo_div_up(a.R, kRaysPerBlock)), dim3(kRayBlock), 0, (hipStream_t)stream, a);
-    NVO_CHECK_LAUNCH();
-    return NVO_OK;
+// workgroups [0, blocks0) serve a0, the rest a1 (blocks1 of them)
+void nvo_ray_legacy_prop_loss(hipStream_t stream, const nvo_prop_loss_args& a0, const nvo_prop_loss_args& a1,
+                              uint32_t blocks0, uint32_t blocks1) {
+    NVO_LAUNCH(k_prop_loss_legacy, dim3(blocks0 + blocks1), dim3(kRayBlock), 0, stream, a0, a1, blocks0);
 }
-
-int nvo_prop_loss(nvo_stream_t stream, const nvo_prop_loss_args* args) {
-    NVO_REQUIRE(args != nullptr, "prop_loss: args is NULL");
-    const nvo_prop_loss_args a = *args;
-    NVO_REQUIRE(a.S >= 1 && a.S <= (uint32_t)kMaxS && a.S_main >= 1 && a.S_main <= 64,
-                "prop_loss: S=%u (<=%d) S_main=%u (<=64)", a.S, kMaxS, a.S_main);
-    NVO_REQUIRE(a.pre && a.x01 && a.sbins && a.tbins && a.sbins_main && a.weights_main && a.losses &&
-                (a.dpre == nullptr || a.dpre_stride >= 1), "prop_loss: NULL input/output");
-    if (a.R == 0) return NVO_OK;
-    NVO_PROF(stream, "prop_loss[S%u]", a.S);
-    const uint32_t blocks = nvo_div_up(a.R, kRaysPerBlock);
-    if (ray_legacy()) nvo_ray_legacy_prop_loss((hipStream_t)stream, a, a, blocks, 0);
-    else NVO_LAUNCH(k_prop_loss, dim3(blocks), dim3(kRayBlock), 0, (hipStream_t)stream, a, a, blocks);
-    NVO_CHECK_LAUNCH();
-    return NVO_OK;
-}
-
-int nvo_prop_loss_pair(nvo_stream_t stream, const nvo_prop_loss_args* args0, const nvo_prop_loss_args* args1) {
-    NVO_REQUIRE(args0 != nullptr && args1 != nullptr, "prop_loss_pair: args is NULL");
-    for (const nvo_prop_loss_args* p : {args0, args1}) {
-        const nvo_prop_loss_args& a = *p;
-        NVO_REQUIRE(a.S >= 1 && a.S <= (uint32_t)kMaxS && a.S_main >= 1 && a.S_main <= 64,
-                    "prop_loss_pair: S=%u (<=%d) S_main=%u (<=64)", a.S, kMaxS, a.S_main);
-        NVO_REQUIRE(a.pre && a.x01 && a.sbins && a.tbins && a.sbins_main && a.weights_main && a.losses &&
-                    (a.dpre == nullptr || a.dpre_stride >= 1), "prop_loss_pair: NULL input/output");
-    }
-    const uint32_t b0 = nvo_div_up(args0->R, kRaysPerBlock), b1 = nvo_div_up(args1->R, kRaysPerBlock);
-    if (b0 + b1 == 0) return NVO_OK;
-    NVO_PROF(stream, "prop_loss[S%u+S%u]", args0->S, args1->S);
-    if (ray_legacy()) nvo_ray_legacy_prop_loss((hipStream_t)stream, *args0, *args1, b0, b1);
-    else NVO_LAUNCH(k_prop_loss, dim3(b0 + b1), dim3(kRayBlock), 0, (hipStream_t)stream, *args0, *args1, b0);
-    NVO_CHECK_LAUNCH();
-    return NVO_OK;
-}
-
-}  // extern "C"
