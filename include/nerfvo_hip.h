@@ -118,6 +118,12 @@ uint64_t nvo_ctx_bytes(nvo_module_t m, uint32_t batch);
  *   "grid_bwd_dense_share"      (with "grid_bwd_batch") chunks of a DENSE slice relative to that even split, in percent
  *                               (default 100; 25..400): 120 when most samples carry a gradient (bf16 gradients, loss
  *                               scale 65536), where dense-level items are the slower kind
+ *   "grid_bwd_scan"             (modes 1 and 3) which form of the slice-owner kernel the launch uses: 1 (default) the
+ *                               instruction-lean scans of grid.hip, 0 the scans as they stood before
+ *                               (csrc/grid_bwd_legacy.hip).  Same item table, scales and live list, same gradient -- bit
+ *                               for bit where the items are single-chunk; tests and A/B timings only.  (The lean hashed
+ *                               scan addresses with 32-bit offsets: a batch of 2^24 samples or more, or a level above
+ *                               2^24 entries, takes the generic per-sample scan without the hit ring -- correct, slower)
  *   "grid_fwd_runs"             the level-major forward (no input gradients requested) walks runs of four consecutive
  *                               samples per thread and gathers only where the cell changes: pays on ray-ordered samples
  *                               of a trained field (inference), costs ~8 % on uniform ones; bit-identical; default 0

@@ -574,6 +574,11 @@ struct GridModule : nvo_module_s {
             slices.runs = stream_bins.owner.runs = value != 0;
             return NVO_OK;
         }
+        if (!strcmp(key, "grid_bwd_scan")) {  // slice-owner kernel: 1 instruction-lean scans (default) | 0 the previous form
+            NVO_REQUIRE(value == 0 || value == 1, "grid_bwd_scan: 0 (legacy) or 1 (lean)");
+            slices.scan = stream_bins.owner.scan = (uint32_t)value;
+            return NVO_OK;
+        }
         if (!strcmp(key, "grid_stream_overlap")) {  // 0: slice-owner levels and record pipeline back to back
             nvo_grid_stream_destroy(&stream_bins);  // (the owner's slice size depends on it)
             stream_bins.overlap = value != 0;

@@ -60,6 +60,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 uint32_t nvo_grid_levels_init(NvoGridLevels* g, uint32_t n_levels, uint32_t n_features,
@@ -1685,23 +1686,49 @@ __device__ __forceinline__ void grid_bwd_item(const NvoGridLevels& g, uint32_t N
             }
             if (open && hit) flush();
         }
-    } else if (pair_bins && ring_off != 0u) {
+    } else if (pair_bins && ring_off != 0u && N < (1u << 24) && size <= (1u << 24)) {
         // HASHED level with a hit queue (kHitCap).  Everything up to the slice test runs for all 64 lanes; the pairs that
-        // fall into this slice (one in `slices of the level` on average) are pushed into the wave's ring -- 16 bytes:
-        // in-slice offset | px << 14, w_y w_z dy_0, w_y w_z dy_1, w_x -- and whenever 64 are waiting the whole wave
-        // splits them into their two x corners and adds them.  The ring is private to the wave (LDS operations of one
-        // wave execute in order: no barrier), head and fill level are wave-uniform scalars, and every push sits in
-        // wave-uniform control flow (a ballot under a lane-divergent branch would let the lanes disagree about them).
-        uint4* const ring = reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(lds_raw) + ring_off) +
-                            (threadIdx.x >> 6) * kHitCap;
+        // fall into this slice (one in `slices of the level` on average) are pushed into the wave's ring -- 16 bytes --
+        // and whenever 64 are waiting the whole wave splits them into their two x corners and adds them.  The ring is
+        // private to the wave (LDS operations of one wave execute in order: no barrier), head and fill level are
+        // wave-uniform scalars, and every push sits in wave-uniform control flow (a ballot under a lane-divergent branch
+        // would let the lanes disagree about them).
+        // The launch is bound by vector-instruction issue, so the scan is written for its
+        // instruction count (EXPERIMENTS.md 12.5; the form before it: grid_bwd_legacy.hip, same bits):
+        //  * byte offsets of 32 bits against wave-uniform bases (N < 2^24 keeps every offset below 2^32; larger batches
+        //    take the generic scan below), all loads of the four samples requested before anything is computed from
+        //    one, 16-bit gradients kept as loaded until their sample's turn;
+        //  * a wave's block that lies wholly inside [begin, end) and walks no list has no per-slot range test and one
+        //    address per array; every other block clamps the slot to the last sample and masks it out of `lv` / `bad`;
+        //  * only index bits below `mask` are ever used and mask < 2^24, so the two hash multiplies are 24-bit ones
+        //    (full rate): the low 24 bits of a product depend on the low 24 bits of its factors alone;
+        //  * a sample without a gradient compares against a slice id that no hash has (one select per sample instead of
+        //    one mask operation per pair), and the ballot comes straight from that compare;
+        //  * 16-bit gradients: an entry is in-slice offset | px << 14, dy as loaded, w_y w_z, w_x and the two products
+        //    w_y w_z dy_f are taken in the drain, where all 64 lanes are busy, not in the push, where an eighth is
+        //    (same operands, same order); fp32 gradients keep offset, w_y w_z dy_0, w_y w_z dy_1, w_x.
+        unsigned char* const ring8 = reinterpret_cast<unsigned char*>(lds_raw) + ring_off + (threadIdx.x >> 6) * (16u * kHitCap);
+        constexpr bool kRawDy = sizeof(DY2) == 4;
         uint32_t q_head = 0u, q_fill = 0u;
         auto q_drain = [&](uint32_t n) {  // the n <= 64 oldest entries
             if (lane_id < n) {
-                uint32_t p = q_head + lane_id;
-                if (p >= kHitCap) p -= kHitCap;
-                const uint4 e = ring[p];
+                const uint32_t p0 = q_head + lane_id;
+                const uint32_t p = min(p0, p0 - kHitCap);  // (p0 < 2 kHitCap: the unsigned difference is huge below kHitCap)
+                // (entries are written and read as four words; the launcher puts the rings at a multiple of 16 bytes)
+                uint4 e;
+                __builtin_memcpy(&e, __builtin_assume_aligned(ring8 + p * 16u, 16), 16);
                 const uint32_t lo = e.x & (ACC::kEntries - 1u), px = e.x >> 14;
-                const float u0 = __uint_as_float(e.y), u1 = __uint_as_float(e.z), wx = __uint_as_float(e.w);
+                float u0, u1;
+                if constexpr (kRawDy) {
+                    const float2 d = dy2f(__builtin_bit_cast(DY2, e.y));
+                    const float w = __uint_as_float(e.z);
+                    u0 = w * d.x;
+                    u1 = w * d.y;
+                } else {
+                    u0 = __uint_as_float(e.y);
+                    u1 = __uint_as_float(e.z);
+                }
+                const float wx = __uint_as_float(e.w);
                 const float wx0 = 1.f - wx;
                 ACC::add(acc, lo ^ px, wx0 * u0, wx0 * u1, sc);
                 ACC::add(acc, lo ^ (px + 1u), wx * u0, wx * u1, sc);
@@ -1710,61 +1737,97 @@ __device__ __forceinline__ void grid_bwd_item(const NvoGridLevels& g, uint32_t N
             if (q_head >= kHitCap) q_head -= kHitCap;
             q_fill -= n;
         };
-        auto q_push = [&](bool hit, uint32_t word, float u0, float u1, float wx) {
-            const unsigned long long m = __ballot(hit);
-            const uint32_t c = (uint32_t)__popcll(m);
-            if (q_fill + c > kHitCap) {  // (cannot happen below 64 waiting entries unless > 63 lanes hit at once)
-                while (q_fill) q_drain(min(q_fill, 64u));
-            }
-            if (hit) {
-                uint32_t p = q_head + q_fill + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                if (p >= kHitCap) p -= kHitCap;
-                ring[p] = make_uint4(word, __float_as_uint(u0), __float_as_uint(u1), __float_as_uint(wx));
-            }
-            q_fill += c;
-            if (q_fill >= 64u) q_drain(64u);
-        };
-        for (uint32_t c0 = wave_grab(64u * kUnroll); begin + c0 < end; c0 = wave_grab(64u * kUnroll)) {
-            const uint32_t i0 = begin + c0 + lane_id;
-            float2 dv[kUnroll];
+        const unsigned char* const x8 = reinterpret_cast<const unsigned char*>(x);
+        const unsigned char* const dy8 = reinterpret_cast<const unsigned char*>(SOA ? dy + (size_t)level * N : dy + level);
+        const unsigned char* const live8 = reinterpret_cast<const unsigned char*>(live);
+        const uint32_t dstride = SOA ? (uint32_t)sizeof(DY2) : g.n_levels * (uint32_t)sizeof(DY2);
+        const uint32_t hmask = mask & ~(ACC::kEntries - 1u);  // the slice bits of an index
+        auto scan_block = [&](uint32_t i0, auto whole_tag) {
+            constexpr bool kWhole = decltype(whole_tag)::value;
+            DY2 raw[kUnroll];
             float xv[kUnroll][3];
-            uint32_t sid[kUnroll];
+            if constexpr (kWhole) {
+                const float* const xp = reinterpret_cast<const float*>(x8 + __umul24(i0, 12u));  // (i0 < N < 2^24)
+                const unsigned char* const dp = dy8 + __umul24(i0, dstride);  // (dstride <= 256)
 #pragma unroll
-            for (uint32_t u = 0; u < kUnroll; ++u) {
-                const uint32_t j = i0 + u * 64u;
-                sid[u] = j < end ? (listed ? live[j] : j) : 0u;
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < kUnroll; ++u) {
-                const uint32_t i = sid[u];
-                dv[u] = make_float2(0.f, 0.f);
-                xv[u][0] = xv[u][1] = xv[u][2] = 0.f;
-                if (i0 + u * 64u < end) {
-                    const DY2 d2 = SOA ? dy[(size_t)level * N + i] : dy[(size_t)i * g.n_levels + level];
-                    dv[u] = dy2f(d2);
-                    xv[u][0] = x[3 * (size_t)i + 0];
-                    xv[u][1] = x[3 * (size_t)i + 1];
-                    xv[u][2] = x[3 * (size_t)i + 2];
+                for (uint32_t u = 0; u < kUnroll; ++u) {
+                    xv[u][0] = xp[u * 192u + 0];
+                    xv[u][1] = xp[u * 192u + 1];
+                    xv[u][2] = xp[u * 192u + 2];
                 }
+#pragma unroll
+                for (uint32_t u = 0; u < kUnroll; ++u) raw[u] = *reinterpret_cast<const DY2*>(dp + u * 64u * dstride);
+            } else {
+                uint32_t sid[kUnroll];
+#pragma unroll
+                for (uint32_t u = 0; u < kUnroll; ++u) sid[u] = min(i0 + u * 64u, end - 1u);
+                if (listed) {  // (one extra round trip per block when the list is used)
+#pragma unroll
+                    for (uint32_t u = 0; u < kUnroll; ++u) sid[u] = *reinterpret_cast<const uint32_t*>(live8 + sid[u] * 4u);
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < kUnroll; ++u) {
+                    const float* const xp = reinterpret_cast<const float*>(x8 + __umul24(sid[u], 12u));
+                    xv[u][0] = xp[0];
+                    xv[u][1] = xp[1];
+                    xv[u][2] = xp[2];
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < kUnroll; ++u) raw[u] = *reinterpret_cast<const DY2*>(dy8 + __umul24(sid[u], dstride));
             }
 #pragma unroll
             for (uint32_t u = 0; u < kUnroll; ++u) {
-                const float2 d = dv[u];
-                bad = bad || !(fabsf(d.x) < INFINITY) || !(fabsf(d.y) < INFINITY);
-                const bool lv = d.x != 0.f || d.y != 0.f;  // (out-of-range slots carry d = 0)
+                const float2 d = dy2f(raw[u]);
+                bool nf = !(fabsf(d.x) < INFINITY) || !(fabsf(d.y) < INFINITY);
+                bool lv = d.x != 0.f || d.y != 0.f;
+                if constexpr (!kWhole) {  // (a slot past the end holds the last sample again: it pushes nothing, flags nothing)
+                    const bool inr = i0 + u * 64u < end;
+                    nf = nf && inr;
+                    lv = lv && inr;
+                }
+                bad = bad || nf;
                 const Corner c = grid_cell(scale, xv[u][0], xv[u][1], xv[u][2]);
                 const float wy0 = 1.f - c.wy, wz0 = 1.f - c.wz;
                 const float wyz[4] = {wy0 * wz0, c.wy * wz0, wy0 * c.wz, c.wy * c.wz};
-                const uint32_t hy0 = c.py * 2654435761u, hy1 = hy0 + 2654435761u;
-                const uint32_t hz0 = c.pz * 805459861u, hz1 = hz0 + 805459861u;
+                const uint32_t hy0 = __umul24(c.py, 2654435761u & 0xFFFFFFu), hy1 = hy0 + 2654435761u;
+                const uint32_t hz0 = __umul24(c.pz, 805459861u & 0xFFFFFFu), hz1 = hz0 + 805459861u;
                 const uint32_t a[4] = {hy0 ^ hz0, hy1 ^ hz0, hy0 ^ hz1, hy1 ^ hz1};
+                const uint32_t want = lv ? first : 0xFFFFFFFFu;  // (no index has the low slice-offset bits set under hmask)
+                const uint32_t pxs = c.px << 14;
+                [[maybe_unused]] uint32_t raw_bits = 0u;
+                if constexpr (kRawDy) raw_bits = __builtin_bit_cast(uint32_t, raw[u]);
 #pragma unroll
                 for (uint32_t j = 0; j < 4; ++j) {
-                    const uint32_t h = a[j] & mask;
-                    q_push(lv && (h & ~(ACC::kEntries - 1u)) == first, (h & (ACC::kEntries - 1u)) | (c.px << 14),
-                           wyz[j] * d.x, wyz[j] * d.y, c.wx);
+                    const bool hit = (a[j] & hmask) == want;
+                    const unsigned long long m = __ballot(hit);
+                    const uint32_t cnt = (uint32_t)__popcll(m);
+                    if (q_fill + cnt > kHitCap) {  // (cannot happen below 64 waiting entries unless > 63 lanes hit at once)
+                        while (q_fill) q_drain(min(q_fill, 64u));
+                    }
+                    if (hit) {
+                        const uint32_t p0 = q_head + q_fill +
+                                            __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                        const uint32_t p = min(p0, p0 - kHitCap);
+                        uint32_t* const w = reinterpret_cast<uint32_t*>(ring8 + p * 16u);
+                        w[0] = (a[j] & (ACC::kEntries - 1u)) | pxs;
+                        if constexpr (kRawDy) {
+                            w[1] = raw_bits;
+                            w[2] = __float_as_uint(wyz[j]);
+                        } else {
+                            w[1] = __float_as_uint(wyz[j] * d.x);
+                            w[2] = __float_as_uint(wyz[j] * d.y);
+                        }
+                        w[3] = __float_as_uint(c.wx);
+                    }
+                    q_fill += cnt;
+                    if (q_fill >= 64u) q_drain(64u);
                 }
             }
+        };
+        for (uint32_t c0 = wave_grab(64u * kUnroll); begin + c0 < end; c0 = wave_grab(64u * kUnroll)) {
+            const uint32_t b0 = begin + c0;  // (wave-uniform)
+            if (!listed && b0 + 64u * kUnroll <= end) scan_block(b0 + lane_id, std::true_type{});
+            else scan_block(b0 + lane_id, std::false_type{});
         }
         while (q_fill) q_drain(min(q_fill, 64u));
     } else
@@ -3583,6 +3646,8 @@ int nvo_grid_bwd_launch(const NvoGridLevels& g, const NvoGridSlices* slices, hip
                            slices->ext_l1, slices->ext_blocks, slices->ext_l1_stride,                                \
                            slices->ext_list ? 1024u : 4096u);                                                   \
     } while (0)
+        if (slices->scan == 0u)  // (option grid_bwd_scan: the previous form of the kernel, same launch)
+            return nvo_grid_bwd_lds_legacy_launch(g, slices, stream, N, x, dy, dy_fmt, soa, grad, lds, ring_off, live);
         if (soa) {
             NVO_DY_DISPATCH(NVO_LAUNCH_LDS, true);
         } else {

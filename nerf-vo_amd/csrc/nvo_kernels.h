@@ -36,6 +36,9 @@ struct NvoGridSlices {
     // consecutive samples, sums the corner contributions in registers while the cell stays the same and goes to the LDS
     // accumulators once per run (consecutive samples are neighbours on a ray, so a coarse cell holds a run of them)
     bool runs = false;
+    // option grid_bwd_scan: 1 (default) the instruction-lean scans of grid.hip, 0 the scans as they stood before
+    // (grid_bwd_legacy.hip: the same-bits reference and the A side of A/B timings).  Chosen per launch, on the host.
+    uint32_t scan = 1;
     // option grid_bwd_batch (set before create): the batch size the launches will see.  With it (and runs) every slice
     // gets the same number of chunks, chosen so that ALL items of the launch are resident at once (one item per CU)
     // and a chunk is a whole number of 8192-sample passes (1024 lanes x 8 consecutive samples): an item costs ~8 us of
@@ -187,6 +190,11 @@ int nvo_grid_bwd_launch(const NvoGridLevels& g, const NvoGridSlices* slices, hip
                         float* grad, int mode);
 // scratch (optional, module-owned): per-level partial gradients [L][N][3] of the two-stage input backward
 typedef NvoScratch NvoGridInputScratch;
+// grid_bwd_legacy.hip: the slice-owner launch of nvo_grid_bwd_launch with the previous kernel (NvoGridSlices::scan == 0);
+// `lds`, `ring_off` and `live` as nvo_grid_bwd_launch worked them out
+int nvo_grid_bwd_lds_legacy_launch(const NvoGridLevels& g, const NvoGridSlices* slices, hipStream_t stream, uint32_t N,
+                                   const float* x, const void* dy, int dy_fmt, bool soa, float* grad, size_t lds,
+                                   uint32_t ring_off, const uint32_t* live);
 int nvo_grid_bwd_input_launch(const NvoGridLevels& g, hipStream_t stream, uint32_t N,
                               const float* x, const void* table_half, const void* dy,
                               int dy_fmt, bool soa, float* dx, bool zero_dx,

@@ -212,6 +212,9 @@ class EngineConfig:
     # proposal networks, module option fuse_encoding: 2 = density network as the epilogue of the small-grid forward
     # (default), 0 = grid kernel + MLP kernel (A/B, tests).  Bit-identical.
     proposal_fuse_encoding: int = 2
+    # slice-owner grid backward, module option grid_bwd_scan: 1 = instruction-lean scans (default), 0 = the previous form of
+    # the kernel (A/B, tests).  Same gradient.
+    grid_bwd_scan: int = 1
     log_every: int = 10                   # LoggingConfig.steps_per_log of the trainer mirror
     seed: int = 1337
 
@@ -279,6 +282,7 @@ class NerfactoEngine:
         for m, per_ray in zip((self.base_net, *self.prop_nets), batches):
             m.set_option("grid_bwd_runs", 1)
             m.set_option("grid_bwd_batch", int(cfg.num_rays * per_ray))
+            m.set_option("grid_bwd_scan", int(cfg.grid_bwd_scan))
         # proposal grids (slice-owner form): int32 accumulators with the overflow-proof L1-derived scale -- half
         # the slices per level and a cheaper conversion (1 M-sample grid 298 -> 227 us, 393 K-sample grid 157 -> 126 us)
         # share of the one-round item table that goes to the dense levels: with most proposal samples carrying a gradient
