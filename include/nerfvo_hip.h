@@ -977,6 +977,58 @@ typedef struct nvo_nn_args {
 } nvo_nn_args;
 int nvo_nn_query(nvo_stream_t stream, const nvo_nn_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * J. Iso-surface of a scalar field sampled on a regular lattice (marching tetrahedra, every vertex owned by its lattice
+ *    edge): the extraction behind render_mesh(source='nerf').  DESIGN.md section 11 states the rule;
+ *    tests/helpers/iso_oracle.py restates it in numpy.
+ *    values [nx][ny][nz] float32, z fastest; valid optional uint8 of the same shape (NULL: every sample is valid);
+ *    nx, ny, nz >= 2 and nx*ny*nz < 2^31.  inside(p) = values[p] > threshold (a NaN is outside).  A cube contributes
+ *    when all eight corners are valid.  Vertex order: ascending (linear index of the edge's lower end, edge kind); face
+ *    order: ascending (cube, tetrahedron, triangle).  vertices [V][3] float32 = lower + g * step per axis with
+ *    g = float(index) + t on the axes the edge runs along, t = clamp((threshold - va) / (vb - va), 0, 1); faces [F][3]
+ *    int32.  Two launches and a prefix sum between them that the CALLER does:
+ *      nvo_iso_count  writes, into scratch, per lattice point the 7-bit mask of cut edges it owns, the rank of its first
+ *                     vertex within its workgroup and the triangle count of its cube, and at the head of scratch
+ *                     int64 totals[2][G]: vertices, then triangles, of each of the G = ceil(nx*ny*nz /
+ *                     points_per_workgroup) workgroups (nvo_iso_workgroups).
+ *      nvo_iso_emit   takes vertex_base / face_base [G] int64 = the EXCLUSIVE prefix sums of those totals and
+ *                     n_vertices / n_faces = their sums, and writes vertices and faces.  V or F >= 2^31 is an error.
+ *    A workgroup owns points_per_workgroup consecutive lattice points (64 .. 2^22); the result is the same bits for
+ *    every value.  No atomics, no workgroup waits for another, no allocation.
+ *    nvo_lattice_positions writes positions [count][3] of the lattice points first .. first+count-1 (z fastest):
+ *    lower + float(index) * step per axis -- the samples NgpEngine.density_lattice evaluates.
+ * ---------------------------------------------------------------------------------------------- */
+#define NVO_ISO_DEFAULT_POINTS_PER_WORKGROUP 4096
+typedef struct nvo_iso_args {
+    const float* values;
+    const uint8_t* valid;        /* optional */
+    void* scratch;               /* nvo_iso_scratch_bytes(nx, ny, nz, points_per_workgroup), 16-byte aligned */
+    const int64_t* vertex_base;  /* emit only: [G] */
+    const int64_t* face_base;    /* emit only: [G] */
+    float* vertices;             /* emit only: [n_vertices][3] */
+    int32_t* faces;              /* emit only: [n_faces][3] */
+    uint64_t n_vertices, n_faces;
+    uint32_t nx, ny, nz;
+    uint32_t points_per_workgroup;
+    float threshold;
+    float lower[3];
+    float step[3];
+} nvo_iso_args;
+uint64_t nvo_iso_workgroups(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t points_per_workgroup);
+uint64_t nvo_iso_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t points_per_workgroup);
+int nvo_iso_count(nvo_stream_t stream, const nvo_iso_args* args);
+int nvo_iso_emit(nvo_stream_t stream, const nvo_iso_args* args);
+
+typedef struct nvo_lattice_args {
+    float* positions;            /* [count][3] */
+    uint64_t first;              /* first + count <= nx*ny*nz */
+    uint32_t count;
+    uint32_t nx, ny, nz;
+    float lower[3];
+    float step[3];
+} nvo_lattice_args;
+int nvo_lattice_positions(nvo_stream_t stream, const nvo_lattice_args* args);
+
 #ifdef __cplusplus
 }
 #endif

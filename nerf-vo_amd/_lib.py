@@ -165,6 +165,22 @@ class NnArgs(C.Structure):
 NN_MAX_CELLS_PER_AXIS = 1024  # NVO_NN_MAX_CELLS_PER_AXIS
 
 
+class IsoArgs(C.Structure):
+    """mirror of nvo_iso_args"""
+    _fields_ = [("values", _p), ("valid", _p), ("scratch", _p), ("vertex_base", _p), ("face_base", _p), ("vertices", _p),
+                ("faces", _p), ("n_vertices", _u64), ("n_faces", _u64), ("nx", _u32), ("ny", _u32), ("nz", _u32),
+                ("points_per_workgroup", _u32), ("threshold", _f), ("lower", _f * 3), ("step", _f * 3)]
+
+
+ISO_DEFAULT_POINTS_PER_WORKGROUP = 4096  # NVO_ISO_DEFAULT_POINTS_PER_WORKGROUP
+
+
+class LatticeArgs(C.Structure):
+    """mirror of nvo_lattice_args"""
+    _fields_ = [("positions", _p), ("first", _u64), ("count", _u32), ("nx", _u32), ("ny", _u32), ("nz", _u32),
+                ("lower", _f * 3), ("step", _f * 3)]
+
+
 _SIGNATURES = {
     "nvo_last_error": (C.c_char_p, []),
     "nvo_version": (_int, []),
@@ -247,6 +263,12 @@ _SIGNATURES = {
     "nvo_tsdf_integrate": (_int, [_p, C.POINTER(TsdfArgs)]),
     # group I
     "nvo_nn_query": (_int, [_p, C.POINTER(NnArgs)]),
+    # group J
+    "nvo_iso_workgroups": (_u64, [_u32, _u32, _u32, _u32]),
+    "nvo_iso_scratch_bytes": (_u64, [_u32, _u32, _u32, _u32]),
+    "nvo_iso_count": (_int, [_p, C.POINTER(IsoArgs)]),
+    "nvo_iso_emit": (_int, [_p, C.POINTER(IsoArgs)]),
+    "nvo_lattice_positions": (_int, [_p, C.POINTER(LatticeArgs)]),
     # group E
     "nvo_adam_step": (_int, [_p, C.POINTER(AdamArgs), _u32, C.POINTER(AdamGroup), C.POINTER(AdamTail)]),
     "nvo_opt_commit": (_int, [_p, C.POINTER(OptCommitArgs), C.POINTER(StepScalars)]),

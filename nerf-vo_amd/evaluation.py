@@ -13,7 +13,8 @@ OpenCV's ``imwrite`` default; 16-bit PNG depth) because OpenCV is not part of th
 pretrained AlexNet weights that cannot be fetched here: ``lpips_loss`` is an optional callable and the
 ``lpips`` column is omitted without it.
 
-3-D (mesh) metrics: ``EvaluationRenderer.render_mesh`` produces the mesh (TSDF fusion of the rendered frames, tsdf.py) and
+3-D (mesh) metrics: ``EvaluationRenderer.render_mesh`` produces the meshes (``source='frames'``: TSDF fusion of the rendered
+frames, tsdf.py; ``source='nerf'``: the model's density iso-surface cropped to the ground-truth mesh's box, meshing.py) and
 ``calculate_metrics_3d`` / ``Evaluator3D`` score it against the ground-truth mesh the way the reference's
 ``calculate_metrics_3d`` (evaluation_utils.py:447-512) and ``Evaluator.calculate_metrics_3d`` (evaluator.py:148-174) do:
 200 000 surface samples per mesh, voxel down-sampling at 1/64, point-to-point ICP of the prediction onto the ground
@@ -220,14 +221,13 @@ class EvaluationRenderer:
         return indices
 
     def render_mesh(self, source: str = "frames", mode: str = "evaluation_frames") -> str:
-        """``mesh/mesh_from_<mode>.ply`` fused from the colour / depth files ``render_frames(mode)`` wrote (rendered first
-        when their folder is absent) at the ground-truth poses of those frames (renderer.py:126-164, 265-273): TSDF fusion
-        on the GPU, nerf_vo_amd/tsdf.py.  Returns the file's path."""
+        """``source='frames'``: ``mesh/mesh_from_<mode>.ply`` fused from the colour / depth files ``render_frames(mode)``
+        wrote (rendered first when their folder is absent) at the ground-truth poses of those frames (renderer.py:126-164,
+        265-273): TSDF fusion on the GPU, nerf_vo_amd/tsdf.py.  ``source='nerf'``: ``mesh/mesh_from_nerf.ply``, the
+        density iso-surface of the model cropped to the ground-truth mesh's box (``_render_mesh_from_nerf``).  Returns the
+        file's path."""
         if source == "nerf":
-            raise NotImplementedError(
-                "render_mesh(source='nerf') (the reference's crop of a density mesh to the ground-truth mesh's bounds) is not "
-                "built; the density mesh itself is: InstantNGPRenderer.render_mesh(file_mesh, resolution, lower_bound, "
-                "upper_bound) / pyngp.Testbed.compute_and_save_marching_cubes_mesh(filename, resolution, aabb)")
+            return self._render_mesh_from_nerf()
         if source != "frames":
             raise NotImplementedError(source)
         from .tsdf import integrate_mesh
@@ -244,6 +244,45 @@ class EvaluationRenderer:
         extrinsics = np.stack([np.asarray(self.dataset.camera_extrinsics[i], dtype=np.float64) for i in indices])
         integrate_mesh(file_mesh=file_mesh, camera_intrinsics=self.dataset.camera_intrinsics, camera_extrinsics=extrinsics,
                        frames_color=colors, frames_depth=depths)
+        return file_mesh
+
+    def _render_mesh_from_nerf(self) -> str:
+        """The reference's ``_render_mesh_from_nerf`` (renderer.py:166-210): the box of the ground-truth mesh's vertices is
+        mapped into the model's frame by inv(matrix_pred2gt_scaled), the model's renderer extracts its density iso-surface
+        over the box of the mapped corners at 1/64 m (``mesh/mesh_from_nerf_raw.ply``), and that mesh, mapped back by
+        matrix_pred2gt_scaled and cropped to the ground-truth box, is ``mesh/mesh_from_nerf.ply``.  Open3D's transform and
+        crop are meshing.transform_mesh / crop_mesh here (parity with Open3D unpinned)."""
+        from .meshing import crop_mesh, read_mesh, transform_mesh, write_mesh
+
+        if not callable(getattr(self.nerf, "render_mesh", None)):
+            raise NotImplementedError(
+                f"render_mesh(source='nerf'): {type(self.nerf).__name__} has no render_mesh(file_mesh, resolution, lower_bound, "
+                "upper_bound).  The occupancy-grid back-end has one (InstantNGPRenderer.render_mesh -> "
+                "pyngp.Testbed.compute_and_save_marching_cubes_mesh); the reference's nerfstudio one is Open3D's Poisson "
+                "reconstruction, which is not built")
+        voxel_size = 1 / 64
+        os.makedirs(f"{self.dir_prediction}/mesh", exist_ok=True)
+        mesh_gt, _ = self.dataset.mesh()
+        points_gt = np.asarray(torch.as_tensor(mesh_gt[0]).detach().cpu().numpy(), dtype=np.float64)
+        lower_gt, upper_gt = points_gt.min(axis=0), points_gt.max(axis=0)
+        corners = np.array([[x, y, z, 1.0] for x in (lower_gt[0], upper_gt[0]) for y in (lower_gt[1], upper_gt[1])
+                            for z in (lower_gt[2], upper_gt[2])])
+        matrix = np.asarray(self.pred2gt_transformation["matrix_pred2gt_scaled"], dtype=np.float64)
+        corners_pred = np.linalg.inv(matrix) @ corners.T  # [4, 8]
+        lower, upper = np.min(corners_pred, axis=1)[:3], np.max(corners_pred, axis=1)[:3]
+        resolution = ((upper - lower) * self.pred2gt_transformation["scale_pred2gt"] / voxel_size).astype(int)
+        file_raw = f"{self.dir_prediction}/mesh/mesh_from_nerf_raw.ply"
+        self.nerf.render_mesh(file_mesh=file_raw, resolution=resolution, lower_bound=lower, upper_bound=upper)
+        vertices, faces = read_mesh(file_raw)[:2]
+        vertices, faces, _ = crop_mesh(transform_mesh(vertices, matrix), faces, lower_gt, upper_gt)
+        if vertices.shape[0] == 0 or faces.shape[0] == 0:
+            raise RuntimeError(
+                f"render_mesh(source='nerf'): nothing of {file_raw} lies inside the ground-truth mesh's box "
+                f"{lower_gt.tolist()} .. {upper_gt.tolist()}, so mesh_from_nerf.ply is not written: the density never crosses the "
+                "iso-surface threshold there (thresh of compute_and_save_marching_cubes_mesh, 2.5 by default) -- train longer or "
+                "extract at a lower thresh")
+        file_mesh = f"{self.dir_prediction}/mesh/mesh_from_nerf.ply"
+        write_mesh(file_mesh, vertices, faces)
         return file_mesh
 
     def export_keyframe_poses(self) -> np.ndarray:

@@ -7,6 +7,12 @@ The surface is extracted with MARCHING TETRAHEDRA -- every grid cube is cut into
 diagonal and each tetrahedron contributes zero, one or two triangles from its four corner signs -- not with the
 256-case marching-cubes tables [UPSTREAM instant-ngp marching_cubes.cu, not vendored]: same iso-surface up to the
 triangulation, no ambiguous cases, and the case table below is generated, not copied.
+
+Two extractors share the tetrahedra, the case table and the winding: ``marching_tetrahedra`` (torch ops on any device: a
+triangle soup whose vertices are merged by quantised position) and ``extract_isosurface`` (the HIP kernels of
+csrc/iso.hip, GPU only: every vertex is owned by its lattice edge), which the density mesh and
+``EvaluationRenderer.render_mesh(source='nerf')`` use.  ``transform_mesh`` / ``crop_mesh`` are the two Open3D steps of the
+reference's ``_render_mesh_from_nerf``.
 """
 from __future__ import annotations
 
@@ -44,6 +50,93 @@ def _case_table():
 _TABLE = _case_table()
 # one corner on the inside of the surface per case (orientation reference; -1: no surface)
 _INSIDE_REF = torch.tensor([next((k for k in range(4) if (case >> k) & 1), -1) if 0 < case < 15 else -1 for case in range(16)])
+
+
+# ---- edge-owned extraction (extract_isosurface, csrc/iso.hip) ----
+# Every tetrahedron edge is a lattice point plus one of these seven offsets (the tetrahedra are the six monotone paths
+# from corner 0 to corner 6, so both ends of an edge are ordered on every axis).  The vertex on a cut edge is owned by
+# the edge's lower end and its kind, which is what makes a merge step unnecessary.
+_EDGE_KINDS = torch.tensor([[1, 0, 0], [0, 1, 0], [0, 0, 1], [1, 1, 0], [0, 1, 1], [1, 0, 1], [1, 1, 1]])
+
+
+def _winding_table():
+    """bool [6 tetrahedra][16 cases][2 triangles]: corners 1 and 2 of the triangle are swapped.  marching_tetrahedra's
+    test (the normal points away from a corner inside the surface) with every cut at its edge's midpoint: the sign of
+    that test does not depend on where along the edges the cuts lie, so it is a function of (tetrahedron, case)."""
+    flip = torch.zeros(6, 16, 2, dtype=torch.bool)
+    corners = _CORNERS.double()
+    for t in range(6):
+        tp = corners[_TETS[t]]  # [4, 3]
+        for case in range(1, 15):
+            pin = tp[int(_INSIDE_REF[case])]
+            for r in range(2):
+                e = _TABLE[case, r]
+                if int(e[0, 0]) < 0:
+                    continue
+                pts = 0.5 * (tp[e[:, 0]] + tp[e[:, 1]])  # [3, 3]
+                nrm = torch.linalg.cross(pts[1] - pts[0], pts[2] - pts[0])
+                s = float((nrm * (pts.mean(dim=0) - pin)).sum())
+                assert s != 0.0
+                flip[t, case, r] = s < 0
+    return flip
+
+
+_WINDING = _winding_table()
+
+
+def iso_edge_table():
+    """The tables csrc/iso_tables.h is generated from (tools/gen_iso_tables.py): ``(count [6][16], edges [6][16][2][3][2])``
+    as nested lists.  ``count`` = triangles of (tetrahedron, case); ``edges[t][case][r][q]`` = (cube corner that owns the
+    q-th vertex of triangle r, edge kind), winding applied; (-1, -1) where there is no triangle."""
+    kinds = [tuple(k) for k in _EDGE_KINDS.tolist()]
+    corners = _CORNERS.tolist()
+    count = [[0] * 16 for _ in range(6)]
+    edges = [[[[[-1, -1] for _ in range(3)] for _ in range(2)] for _ in range(16)] for _ in range(6)]
+    for t in range(6):
+        tet = _TETS[t].tolist()
+        for case in range(16):
+            for r in range(2):
+                e = _TABLE[case, r].tolist()
+                if e[0][0] < 0:
+                    continue
+                count[t][case] += 1
+                order = [0, 2, 1] if bool(_WINDING[t, case, r]) else [0, 1, 2]
+                for q, src in enumerate(order):
+                    ca, cb = tet[e[src][0]], tet[e[src][1]]
+                    d = [b - a for a, b in zip(corners[ca], corners[cb])]
+                    if min(d) < 0:
+                        ca, cb, d = cb, ca, [-x for x in d]
+                    assert min(d) >= 0 and tuple(d) in kinds, "a tetrahedron edge that is not one of the seven kinds"
+                    edges[t][case][r][q] = [ca, kinds.index(tuple(d))]
+    return count, edges
+
+
+def iso_tables_header() -> str:
+    """Text of csrc/iso_tables.h (tools/gen_iso_tables.py writes it; tests/test_iso_cpu.py compares)."""
+    count, edges = iso_edge_table()
+    corners, kinds = _CORNERS.tolist(), _EDGE_KINDS.tolist()
+    kind_corner = [corners.index(k) for k in kinds]
+
+    def rows(values, fmt):
+        return ",\n".join("    {" + ", ".join(fmt(v) for v in row) + "}" for row in values)
+
+    packed = [[[(e[0] << 3 | e[1]) if e[0] >= 0 else 255 for tri in edges[t][case] for e in tri] for case in range(16)]
+              for t in range(6)]
+    out = ["// GENERATED by tools/gen_iso_tables.py from nerf_vo_amd/meshing.py (_CORNERS, _TETS, _TABLE, _WINDING, _EDGE_KINDS).",
+           "// Do not edit: tests/test_iso_cpu.py regenerates the text and compares.", "#pragma once", "",
+           "// cube corner m -> (x, y, z) offset", "static __constant__ const unsigned char kIsoCorner[8][3] = {",
+           rows(corners, str), "};", "", "// edge kind -> (x, y, z) offset of the far end, and that offset's cube corner",
+           "static __constant__ const unsigned char kIsoKind[7][3] = {", rows(kinds, str), "};",
+           "static __constant__ const unsigned char kIsoKindCorner[7] = {" + ", ".join(map(str, kind_corner)) + "};", "",
+           "// the six tetrahedra around the diagonal 0-6: cube corners of tetrahedron corners 0..3",
+           "static __constant__ const unsigned char kIsoTet[6][4] = {", rows(_TETS.tolist(), str), "};", "",
+           "// triangles of (tetrahedron, case), case = sum of inside(tetrahedron corner m) << m",
+           "static __constant__ const unsigned char kIsoTriCount[6][16] = {", rows(count, str), "};", "",
+           "// [tetrahedron][case][2 triangles x 3 vertices]: (owning cube corner << 3) | edge kind, winding applied; 255: none",
+           "static __constant__ const unsigned char kIsoTriEdge[6][16][6] = {"]
+    out.append(",\n".join("    {\n" + rows(packed[t], lambda v: f"{v:3d}").replace("    {", "        {") + "\n    }" for t in range(6)))
+    out += ["};", ""]
+    return "\n".join(out)
 
 
 @torch.no_grad()
@@ -114,6 +207,88 @@ def marching_tetrahedra(values: torch.Tensor, lower, upper, threshold: float, sl
     faces = inverse.view(-1, 3)
     faces = faces[(faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])]
     return lo + verts * step, faces
+
+
+@torch.no_grad()
+def extract_isosurface(values: torch.Tensor, lower, upper, threshold: float, valid=None, points_per_workgroup: int = None):
+    """The iso-surface of ``values`` [nx, ny, nz] (samples at the corners of a regular lattice spanning [lower, upper]) at
+    ``threshold`` -> (vertices float32 [V, 3], faces int64 [F, 3]) on the samples' GPU, by the HIP extractor
+    (csrc/iso.hip; the rule is DESIGN.md section 11): the surface of ``marching_tetrahedra`` -- same tetrahedra, same case
+    table, same winding -- with every vertex owned by its lattice edge, so there is no merge step, no crack where two
+    copies of a vertex round differently, and the result is the same bits from run to run.  ``valid`` (bool or uint8
+    [nx, ny, nz]): a cube contributes only if all eight corners are valid.  Zero-area triangles (a sample exactly on the
+    threshold) are kept.  ``points_per_workgroup`` is a launch parameter: the result does not depend on it."""
+    import ctypes as C
+
+    from . import _lib
+
+    if not (torch.is_tensor(values) and values.is_cuda):
+        raise RuntimeError("extract_isosurface: the samples must be on the GPU -- no CPU fallback (marching_tetrahedra is the "
+                           "torch extractor)")
+    if values.dim() != 3 or min(values.shape) < 2 or values.numel() >= 2 ** 31:
+        raise ValueError(f"extract_isosurface: values [nx, ny, nz] with at least 2 samples per axis and fewer than 2^31 in all "
+                         f"expected, got {tuple(values.shape)}")
+    dev = values.device
+    values = values.to(torch.float32).contiguous()
+    nx, ny, nz = values.shape
+    if valid is not None:
+        if tuple(valid.shape) != (nx, ny, nz):
+            raise ValueError(f"extract_isosurface: valid {tuple(valid.shape)} does not match values {(nx, ny, nz)}")
+        valid = valid.to(device=dev, dtype=torch.uint8).contiguous()
+    lo = np.asarray(lower.detach().cpu().numpy() if torch.is_tensor(lower) else lower, dtype=np.float32).reshape(3)
+    hi = np.asarray(upper.detach().cpu().numpy() if torch.is_tensor(upper) else upper, dtype=np.float32).reshape(3)
+    step = (hi - lo) / np.asarray([nx - 1, ny - 1, nz - 1], dtype=np.float32)  # float32, as marching_tetrahedra
+    ppw = int(_lib.ISO_DEFAULT_POINTS_PER_WORKGROUP if points_per_workgroup is None else points_per_workgroup)
+    lib = _lib.lib()
+    groups = int(lib.nvo_iso_workgroups(nx, ny, nz, ppw))
+    scratch = torch.empty(int(lib.nvo_iso_scratch_bytes(nx, ny, nz, ppw)), dtype=torch.uint8, device=dev)
+    args = _lib.IsoArgs(values=values.data_ptr(), valid=None if valid is None else valid.data_ptr(), scratch=scratch.data_ptr(),
+                        nx=nx, ny=ny, nz=nz, points_per_workgroup=ppw, threshold=float(threshold),
+                        lower=(C.c_float * 3)(*lo.tolist()), step=(C.c_float * 3)(*step.tolist()))
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.nvo_iso_count(stream, C.byref(args)), "iso_count")
+        totals = scratch[:16 * groups].view(torch.int64).view(2, groups)
+        ends = torch.cumsum(totals, dim=1)
+        bases = (ends - totals).contiguous()
+        n_vert, n_face = (int(x) for x in ends[:, -1].tolist())
+        if n_vert >= 2 ** 31 or n_face >= 2 ** 31:
+            raise RuntimeError(f"extract_isosurface: {n_vert} vertices and {n_face} faces -- each must stay below 2^31; extract a "
+                               "smaller box or a coarser lattice")
+        vertices = torch.empty(n_vert, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(n_face, 3, dtype=torch.int32, device=dev)
+        if n_vert or n_face:
+            args.vertex_base, args.face_base = bases[0].data_ptr(), bases[1].data_ptr()
+            args.vertices, args.faces = vertices.data_ptr(), faces.data_ptr()
+            args.n_vertices, args.n_faces = n_vert, n_face
+            _lib.check(lib.nvo_iso_emit(stream, C.byref(args)), "iso_emit")
+    return vertices, faces.long()
+
+
+def transform_mesh(vertices, matrix) -> torch.Tensor:
+    """vertices [V, 3] mapped by the 4 x 4 ``matrix`` (rotation, scale and translation: its last row is ignored), in
+    float64, returned as float32 on the vertices' device.  Row r is ``((m[r][0]*x + m[r][1]*y) + m[r][2]*z) + m[r][3]``,
+    one product or sum per step (no matrix product, whose summation order is the BLAS library's): the result is the same
+    bits wherever it is computed."""
+    v = torch.as_tensor(vertices).to(torch.float64)
+    m = np.asarray(matrix, dtype=np.float64)
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    rows = [((float(m[r, 0]) * x + float(m[r, 1]) * y) + float(m[r, 2]) * z) + float(m[r, 3]) for r in range(3)]
+    return torch.stack(rows, dim=1).to(torch.float32)
+
+
+def crop_mesh(vertices, faces, lower, upper):
+    """The part of a mesh inside the axis-aligned box: vertices with ``lower <= v <= upper`` on every axis, faces all
+    three of whose vertices are kept, re-indexed, both in their order (the rule Open3D documents for
+    ``TriangleMesh.crop``; parity with Open3D is unpinned) -> (vertices, faces, kept bool [V])."""
+    v, f = torch.as_tensor(vertices), torch.as_tensor(faces).long()
+    lo = torch.as_tensor(np.asarray(lower, dtype=np.float64)).to(v.device)
+    hi = torch.as_tensor(np.asarray(upper, dtype=np.float64)).to(v.device)
+    v64 = v.to(torch.float64)
+    keep = ((v64 >= lo) & (v64 <= hi)).all(dim=1)
+    new_index = torch.cumsum(keep.long(), dim=0) - 1
+    f = f[keep[f].all(dim=1)] if f.numel() else f.reshape(0, 3)
+    return v[keep], new_index[f], keep
 
 
 def write_mesh(path: str, vertices: torch.Tensor, faces: torch.Tensor, colors=None, normals=None) -> None:

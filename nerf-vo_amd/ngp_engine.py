@@ -1077,12 +1077,55 @@ class NgpEngine:
         for c0 in range(0, M, chunk):
             p = positions[c0:c0 + chunk].to(self.device, torch.float32)
             n = p.shape[0]
-            x01.zero_()
-            x01[:n] = ((p - lo) / (hi - lo)).clamp_(0.0, 1.0)
-            _call("nvo_fwd", self.density_net.handle, stream, chunk, _ptr(x01), self._pp("density", ph), _ptr(out), _ptr(ctx))
-            inside = ((p >= lo) & (p <= hi)).all(dim=1)
-            res[c0:c0 + n] = torch.where(inside, torch.exp(out[:n, 0].float().clamp(max=15.0)), torch.zeros((), device=self.device))
+            res[c0:c0 + n] = self._density_of(p, n, x01, out, ctx, ph, stream)
         return res
+
+    @torch.no_grad()
+    def density_lattice(self, lower, upper, res, chunk: int = 1 << 20) -> torch.Tensor:
+        """``density_at`` on the regular lattice of ``res`` = (rx, ry, rz) samples spanning [lower, upper] of the engine's
+        normalised frame -> float32 [rx, ry, rz].  Sample i of an axis lies at ``lower + float(i) * step`` in float32 with
+        ``step = (upper - lower) / (r - 1)`` in float32: the step ``meshing.extract_isosurface`` computes from the same
+        bounds, so an extracted vertex lies exactly between two positions that were sampled.  Positions are generated per
+        chunk from the lattice indices (csrc/iso.hip, nvo_lattice_positions): no [n, 3] tensor of the whole lattice exists
+        and the memory beside the result is bounded by ``chunk``."""
+        import numpy as np
+
+        r = [int(x) for x in np.asarray(res).reshape(-1).tolist()]
+        if len(r) != 3 or min(r) < 2 or r[0] * r[1] * r[2] >= 2 ** 31:
+            raise ValueError(f"density_lattice: res {r} -- three axes of at least 2 samples and fewer than 2^31 samples in all are "
+                             "needed (the extractor addresses a lattice with 32-bit indices): lower the resolution or cut the box "
+                             "into several calls")
+        lo = np.asarray(lower, dtype=np.float32).reshape(3)
+        hi = np.asarray(upper, dtype=np.float32).reshape(3)
+        step = (hi - lo) / np.asarray([r[0] - 1, r[1] - 1, r[2] - 1], dtype=np.float32)
+        n = r[0] * r[1] * r[2]
+        chunk = max(256, (min(int(chunk), n) + 255) // 256 * 256)
+        stream = _stream(self.device)
+        pos = torch.zeros(chunk, 3, device=self.device)
+        x01 = torch.empty(chunk, 3, device=self.device)
+        out = torch.empty(chunk, 16, dtype=torch.float16, device=self.device)
+        ctx = torch.empty(self.density_net.ctx_bytes(chunk), dtype=torch.uint8, device=self.device)
+        res_flat = torch.empty(n, device=self.device)
+        ph = self.inference_params_half()
+        args = _lib.LatticeArgs(positions=pos.data_ptr(), nx=r[0], ny=r[1], nz=r[2], lower=(C.c_float * 3)(*lo.tolist()),
+                                step=(C.c_float * 3)(*step.tolist()))
+        for c0 in range(0, n, chunk):
+            m = min(chunk, n - c0)
+            args.first, args.count = c0, m
+            _call("nvo_lattice_positions", stream, C.byref(args))
+            res_flat[c0:c0 + m] = self._density_of(pos, m, x01, out, ctx, ph, stream)
+        return res_flat.view(r[0], r[1], r[2])
+
+    def _density_of(self, p, n, x01, out, ctx, ph, stream) -> torch.Tensor:
+        """density of the first n rows of p [chunk, 3] (float32, the engine's device): the rule of ``density_at``"""
+        lo, hi = self.cfg.aabb
+        chunk = x01.shape[0]
+        p = p[:n]
+        x01.zero_()
+        x01[:n] = ((p - lo) / (hi - lo)).clamp_(0.0, 1.0)
+        _call("nvo_fwd", self.density_net.handle, stream, chunk, _ptr(x01), self._pp("density", ph), _ptr(out), _ptr(ctx))
+        inside = ((p >= lo) & (p <= hi)).all(dim=1)
+        return torch.where(inside, torch.exp(out[:n, 0].float().clamp(max=15.0)), torch.zeros((), device=self.device))
 
     def loss_dict(self) -> dict:
         vals = self.losses.sum(dim=0).tolist()

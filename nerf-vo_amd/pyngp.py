@@ -29,7 +29,7 @@ reference tree; this facade is pinned to the reference's call sites, which is al
 Differences from the CUDA testbed, all outside what the reference observes: training data may be handed over as
 device tensors (no host round trip); snapshots are msgpack containers with this module's own schema (the upstream
 .msgpack layout is [UPSTREAM]); ``render`` always uses spp = 1 rays through pixel centres; the mesh of
-``compute_and_save_marching_cubes_mesh`` is extracted with marching tetrahedra (meshing.py).  There is no CPU fallback: the engine needs the HIP library and an MI355X.
+``compute_and_save_marching_cubes_mesh`` is extracted with marching tetrahedra (meshing.extract_isosurface, csrc/iso.hip).  There is no CPU fallback: the engine needs the HIP library and an MI355X.
 """
 from __future__ import annotations
 
@@ -413,11 +413,14 @@ class Testbed:
     def compute_and_save_marching_cubes_mesh(self, filename: str, resolution=(256, 256, 256), aabb: BoundingBox | None = None,
                                              thresh: float = 2.5, generate_uvs_for_obj_file: bool = False) -> None:
         """Density iso-surface at ``thresh`` (instant-ngp's default 2.5) over ``aabb`` (dataset / world coordinates, as
-        the reference passes it: nerf_renderer.py:296-300; empty or infinite -> the scene box) sampled on a
-        ``resolution`` grid, written as .obj or .ply.  The surface is extracted with marching tetrahedra
-        (nerf_vo_amd/meshing.py) instead of upstream's marching-cubes tables: same iso-surface, another triangulation.
-        Vertices are written in the same dataset coordinates the box is given in."""
-        from .meshing import marching_tetrahedra, write_mesh
+        the reference passes it: nerf_renderer.py:296-300; empty or infinite -> the scene box; clamped to the scene box)
+        sampled on a lattice of ``resolution`` samples per axis, written as .obj or .ply (positions only: 12 bytes per
+        vertex in a .ply).  The density is evaluated by ``NgpEngine.density_lattice`` (positions generated per chunk from
+        the lattice indices) and the surface extracted by the HIP extractor ``meshing.extract_isosurface`` (marching
+        tetrahedra with every vertex owned by its lattice edge) instead of upstream's marching-cubes
+        tables: same iso-surface, another triangulation.  Both work in the engine's normalised frame; the vertices are
+        mapped back (in float64) and written in the same dataset coordinates the box is given in."""
+        from .meshing import extract_isosurface, write_mesh
 
         if self._engine is None:
             raise RuntimeError("compute_and_save_marching_cubes_mesh: no network has been trained or loaded")
@@ -434,11 +437,10 @@ class Testbed:
         if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
             lo, hi = world_lo, world_hi
         lo, hi = np.maximum(lo, world_lo), np.minimum(hi, world_hi)
-        axes = [torch.linspace(float(lo[k]), float(hi[k]), res[k], device=self.device) for k in range(3)]
-        gx, gy, gz = torch.meshgrid(*axes, indexing="ij")
-        world = torch.stack([gx, gy, gz], dim=-1).reshape(-1, 3)
-        unit = world * scale + torch.as_tensor(off, dtype=torch.float32, device=self.device)
-        dens = e.density_at(unit).view(*res)
-        verts, faces = marching_tetrahedra(dens, lo, hi, float(thresh))
+        unit_lo, unit_hi = lo * scale + off, hi * scale + off
+        dens = e.density_lattice(unit_lo, unit_hi, res)
+        verts, faces = extract_isosurface(dens, unit_lo, unit_hi, float(thresh))
+        del dens
+        verts = ((verts.double() - torch.as_tensor(off, device=verts.device)) / scale).float()
         os.makedirs(os.path.dirname(os.path.abspath(filename)), exist_ok=True)
         write_mesh(filename, verts, faces)

@@ -105,10 +105,13 @@ def _log(mapper):
 
 def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, eval_frames=8, chunk=8, device="cuda:0",
         camera_optimizer_mode=None, pose_noise=None, deterministic=False, seed=42, dynamic_loss_scale=None, out_dir=None,
-        quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None, mesh=False, metrics_3d=False):
+        quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None, mesh=False, metrics_3d=False,
+        mesh_nerf=False):
     """``method``: 'nerfstudio' (the default mapper) or 'instant-ngp' (the occupancy-grid back-end through the pyngp facade,
     /root/reference/nerf_vo/mapping/instant_ngp.py + evaluation/nerf_renderer.py:221-320; the room is shrunk by
-    ``scene_scale``, default 0.5, so that it lies inside that back-end's scene box: it takes poses as they come)."""
+    ``scene_scale``, default 0.5, so that it lies inside that back-end's scene box: it takes poses as they come).
+    ``mesh_nerf`` (instant-ngp only): also ``render_mesh(source='nerf')``, the density iso-surface cropped to the ground-truth
+    mesh's box (run.py:72); with ``metrics_3d`` the table gains its row."""
     entry.build()
     from nerf_vo_amd.evaluation import (EvaluationRenderer, Evaluator2D, Evaluator3D, read_color, transform_matrices_pred2gt)
     from nerf_vo_amd.mapping.dataset import opencv_to_opengl
@@ -122,6 +125,8 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
     out_dir = out_dir or tempfile.mkdtemp(prefix="nvo_eval_")
     n_frames = keyframes * frame_stride  # dataset frames; every frame_stride-th one is a keyframe (configs: frame_stride 2)
     ngp = method == "instant-ngp"
+    if mesh_nerf and not ngp:
+        raise SystemExit("--mesh-nerf needs --method instant-ngp (the nerfstudio back-end has no density mesh)")
     if ngp and abs(width / height - 1200.0 / 680.0) > 0.01:
         # (the testbed's free camera has ONE focal length, evaluation/nerf_renderer.py:152: Replica's intrinsics have square
         # pixels only at its own aspect -- 160 x 120 renders with fx != fy come out at 13 dB)
@@ -184,11 +189,24 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
         file_mesh = renderer.render_mesh(source="frames", mode="evaluation_frames")
         mesh_info = {"file": file_mesh if not own_dir else os.path.basename(file_mesh), "bytes": os.path.getsize(file_mesh),
                      "seconds": time.perf_counter() - t_mesh}
+    mesh_nerf_info = None
+    if mesh_nerf:  # run.py:72: mesh/mesh_from_nerf_raw.ply and its crop mesh/mesh_from_nerf.ply
+        t_mesh = time.perf_counter()
+        file_mesh = renderer.render_mesh(source="nerf")
+        mesh_nerf_info = {"file": file_mesh if not own_dir else os.path.basename(file_mesh), "bytes": os.path.getsize(file_mesh),
+                          "seconds": time.perf_counter() - t_mesh}
     m_3d = None
     if metrics_3d:  # run.py:79: ground-truth mesh fused from all ground-truth frames, results/metrics_3d.csv
+        import pandas as pd
+
         t_3d = time.perf_counter()
-        m_3d = Evaluator3D(ds, args.dir_prediction, out_dir + "/results").calculate_metrics_3d()
-        m_3d = {**{k: float(v) for k, v in m_3d.items()}, "seconds_incl_ground_truth_mesh": time.perf_counter() - t_3d}
+        Evaluator3D(ds, args.dir_prediction, out_dir + "/results").calculate_metrics_3d()
+        seconds_3d = time.perf_counter() - t_3d
+        table = pd.read_csv(out_dir + "/results/metrics_3d.csv").set_index("mesh")
+        m_3d = {**{k: float(v) for k, v in table.loc["mesh_from_evaluation_frames"].items()},
+                "seconds_incl_ground_truth_mesh": seconds_3d}
+        if "mesh_from_nerf" in table.index:
+            m_3d["mesh_from_nerf"] = {k: float(v) for k, v in table.loc["mesh_from_nerf"].items()}
     ev = Evaluator2D(ds, kf, args.dir_prediction, out_dir + "/results")
     m_eval = ev.calculate_metrics_2d(mode="evaluation_frames")
     m_kf = {}
@@ -221,6 +239,8 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
            "deterministic": bool(deterministic), "seed": seed, "exported_poses": int(exported.shape[0])}
     if mesh_info is not None:
         res["mesh"] = mesh_info
+    if mesh_nerf_info is not None:
+        res["mesh_nerf"] = mesh_nerf_info
     if m_3d is not None:
         res["metrics_3d"] = m_3d
     if ngp:
@@ -254,8 +274,10 @@ if __name__ == "__main__":
     ap.add_argument("--mesh", action="store_true", help="also fuse the rendered evaluation frames into mesh/mesh_from_evaluation_frames.ply")
     ap.add_argument("--metrics-3d", action="store_true", help="also score the mesh against the fused ground-truth mesh "
                     "(results/metrics_3d.csv); implies --mesh")
+    ap.add_argument("--mesh-nerf", action="store_true", help="instant-ngp only: also extract the density iso-surface, cropped to "
+                    "the ground-truth mesh's box (mesh/mesh_from_nerf.ply); with --metrics-3d the table gains its row")
     a = ap.parse_args()
     run(a.keyframes, a.height, a.width, a.iterations, eval_frames=a.eval_frames, camera_optimizer_mode=a.camera_optimizer_mode,
         pose_noise=a.pose_noise, deterministic=a.deterministic, seed=a.seed, quiet=False,
         dynamic_loss_scale=False if a.static_loss_scale else None, keyframe_views=not a.no_keyframe_views,
-        method=a.method, scene_scale=a.scene_scale, mesh=a.mesh, metrics_3d=a.metrics_3d)
+        method=a.method, scene_scale=a.scene_scale, mesh=a.mesh, metrics_3d=a.metrics_3d, mesh_nerf=a.mesh_nerf)
