@@ -1284,14 +1284,9 @@ def test_pose_bwd_lds_table_matches_global_atomics(device, R, F):
         _call(name, _stream(device), R, _ptr(idx), _ptr(dev[0]), _ptr(dev[1]), _ptr(dev[2]), _ptr(dev[3]), _ptr(dev[4]),
               _ptr(acc), *extra)
         out[name] = acc.cpu().double()
-    cam, py, px = idx[:, 0].cpu(), idx[:, 1].cpu().double() + 0.5, idx[:, 2].cpu().double() + 0.5
-    it = intr.double()[cam]
-    raw = torch.stack([(px - it[:, 2]) / it[:, 0], -(py - it[:, 3]) / it[:, 1], -torch.ones(R, dtype=torch.float64)], dim=1)
-    d0 = torch.einsum("rij,rj->ri", c2w.double()[cam][:, :, :3], raw)
-    d0 = d0 / d0.norm(dim=1, keepdim=True)
-    gd = d_d.double() + 0.5 * d_d01.double()
-    per_ray = torch.cat([gd[:, :, None] * d0[:, None, :], d_o.double()[:, :, None]], dim=2)  # [R][3][4]
-    ref = torch.zeros(F, 3, 4, dtype=torch.float64).index_add_(0, cam, per_ray)
+    from helpers.pose_oracle import pose_chain  # the float64 sum (tests/test_pose_chain_gpu.py holds it to float32 bounds)
+
+    ref = pose_chain(idx.cpu(), intr, c2w, d_o, d_d, d_d01, F)
     tol = 1e-4 * float(ref.abs().max())
     for name, got in out.items():
         assert float((got - ref).abs().max()) <= tol, (name, float((got - ref).abs().max()), tol)
