@@ -1029,6 +1029,39 @@ typedef struct nvo_lattice_args {
 } nvo_lattice_args;
 int nvo_lattice_positions(nvo_stream_t stream, const nvo_lattice_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * K. Exact k nearest neighbours of N points among M target points binned into the cell grid of section I (same grid,
+ *    same cell rule, same clamping of the query's cell, same cap of NVO_NN_MAX_CELLS_PER_AXIS cells per axis): the search
+ *    behind the statistical outlier removal of the nerfacto point cloud (the reference gets it from Open3D's
+ *    remove_statistical_outlier on the CPU).  DESIGN.md "k nearest neighbours and the point cloud" states the rule and the
+ *    termination argument; tests/helpers/knn_oracle.py restates it by brute force.
+ *    d2(p) = (dx*dx + dy*dy) + dz*dz in fp32, d = query - point, over ALL M points (a cloud that queries itself finds each
+ *    point at distance 0).  The result is the k smallest pairs (d2, original index) in lexicographic order, ties on d2 going
+ *    to the smaller index: out_dist2 [N][k] and out_index [N][k] in that order; with M < k the slots from M on hold +inf
+ *    and -1.  1 <= k <= NVO_KNN_MAX_K; with k = 1 the two tables are nvo_nn_query's outputs (unbounded, no transform) bit
+ *    for bit.  Optional out_mean_dist [N] = (((s_0 + s_1) + ...) + s_{c-1}) / float(c) with s_j = sqrt(d2_j) and
+ *    c = min(k, M), in fp32, summed in the output's ascending order, square root and division correctly rounded.  The
+ *    table pair or out_mean_dist may be NULL, not both (out_dist2 and out_index are NULL together).  The result is that
+ *    of the brute-force evaluation bit for bit, whatever the cell size, the grid dimensions, the launch shape and the
+ *    order of the queries.  No atomics, no allocation, no dependency between queries.
+ * ---------------------------------------------------------------------------------------------- */
+#define NVO_KNN_MAX_K 32
+typedef struct nvo_knn_args {
+    const float* points;         /* [M][3], sorted by cell */
+    const uint32_t* point_index; /* [M] */
+    const uint32_t* cell_start;  /* [gx*gy*gz + 1] */
+    const float* queries;        /* [N][3] */
+    float* out_dist2;            /* [N][k], optional (with out_index) */
+    int32_t* out_index;          /* [N][k], optional (with out_dist2) */
+    float* out_mean_dist;        /* [N], optional */
+    uint32_t N, M;               /* 1 .. 2^31 - 1 each */
+    uint32_t k;                  /* 1 .. NVO_KNN_MAX_K */
+    uint32_t gx, gy, gz;
+    float lower_x, lower_y, lower_z;
+    float cell_size;             /* > 0, finite */
+} nvo_knn_args;
+int nvo_knn_query(nvo_stream_t stream, const nvo_knn_args* args);
+
 #ifdef __cplusplus
 }
 #endif

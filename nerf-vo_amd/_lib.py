@@ -165,6 +165,16 @@ class NnArgs(C.Structure):
 NN_MAX_CELLS_PER_AXIS = 1024  # NVO_NN_MAX_CELLS_PER_AXIS
 
 
+class KnnArgs(C.Structure):
+    """mirror of nvo_knn_args"""
+    _fields_ = [("points", _p), ("point_index", _p), ("cell_start", _p), ("queries", _p), ("out_dist2", _p), ("out_index", _p),
+                ("out_mean_dist", _p), ("N", _u32), ("M", _u32), ("k", _u32), ("gx", _u32), ("gy", _u32), ("gz", _u32),
+                ("lower_x", _f), ("lower_y", _f), ("lower_z", _f), ("cell_size", _f)]
+
+
+KNN_MAX_K = 32  # NVO_KNN_MAX_K
+
+
 class IsoArgs(C.Structure):
     """mirror of nvo_iso_args"""
     _fields_ = [("values", _p), ("valid", _p), ("scratch", _p), ("vertex_base", _p), ("face_base", _p), ("vertices", _p),
@@ -269,6 +279,8 @@ _SIGNATURES = {
     "nvo_iso_count": (_int, [_p, C.POINTER(IsoArgs)]),
     "nvo_iso_emit": (_int, [_p, C.POINTER(IsoArgs)]),
     "nvo_lattice_positions": (_int, [_p, C.POINTER(LatticeArgs)]),
+    # group K
+    "nvo_knn_query": (_int, [_p, C.POINTER(KnnArgs)]),
     # group E
     "nvo_adam_step": (_int, [_p, C.POINTER(AdamArgs), _u32, C.POINTER(AdamGroup), C.POINTER(AdamTail)]),
     "nvo_opt_commit": (_int, [_p, C.POINTER(OptCommitArgs), C.POINTER(StepScalars)]),

@@ -20,7 +20,10 @@ frames, tsdf.py; ``source='nerf'``: the model's density iso-surface cropped to t
 200 000 surface samples per mesh, voxel down-sampling at 1/64, point-to-point ICP of the prediction onto the ground
 truth, nearest-neighbour distances both ways, ``accuracy / completion / precision / recall / f1score`` at 0.05.  The
 reference uses Open3D and scipy on the CPU; here pointcloud.py does the cloud operations and the nearest-neighbour search
-is a HIP kernel (csrc/nn.hip).
+is a HIP kernel (csrc/nn.hip).  For the nerfstudio back-end, whose density mesh in the reference is a point cloud
+followed by Open3D's Poisson reconstruction, ``EvaluationRenderer.render_point_cloud`` produces the cloud
+(``pointcloud/pointcloud_from_nerf.ply``; mapping/renderer.py, the k-NN kernel csrc/knn.hip under its outlier removal) and
+``calculate_metrics_3d_cloud`` / ``Evaluator3D.calculate_metrics_3d_clouds`` score it as a cloud; the reconstruction is not built.
 
 The numeric functions are pinned by the reference's own outputs: tests/golden/make_golden_evaluation.py and
 make_golden_metrics3d.py execute the reference's definitions on seeded inputs and tests/test_evaluation_cpu.py /
@@ -246,6 +249,20 @@ class EvaluationRenderer:
                        frames_color=colors, frames_depth=depths)
         return file_mesh
 
+    def _ground_truth_box_in_model_frame(self) -> tuple:
+        """``(lower_gt, upper_gt, matrix, lower, upper)``: the box of the ground-truth mesh's vertices, matrix_pred2gt_scaled,
+        and the box of that box's eight corners mapped into the model's frame by its inverse (float64) -- shared by the
+        density mesh and the point cloud."""
+        mesh_gt, _ = self.dataset.mesh()
+        points_gt = np.asarray(torch.as_tensor(mesh_gt[0]).detach().cpu().numpy(), dtype=np.float64)
+        lower_gt, upper_gt = points_gt.min(axis=0), points_gt.max(axis=0)
+        corners = np.array([[x, y, z, 1.0] for x in (lower_gt[0], upper_gt[0]) for y in (lower_gt[1], upper_gt[1])
+                            for z in (lower_gt[2], upper_gt[2])])
+        matrix = np.asarray(self.pred2gt_transformation["matrix_pred2gt_scaled"], dtype=np.float64)
+        corners_pred = np.linalg.inv(matrix) @ corners.T  # [4, 8]
+        lower, upper = np.min(corners_pred, axis=1)[:3], np.max(corners_pred, axis=1)[:3]
+        return lower_gt, upper_gt, matrix, lower, upper
+
     def _render_mesh_from_nerf(self) -> str:
         """The reference's ``_render_mesh_from_nerf`` (renderer.py:166-210): the box of the ground-truth mesh's vertices is
         mapped into the model's frame by inv(matrix_pred2gt_scaled), the model's renderer extracts its density iso-surface
@@ -258,18 +275,12 @@ class EvaluationRenderer:
             raise NotImplementedError(
                 f"render_mesh(source='nerf'): {type(self.nerf).__name__} has no render_mesh(file_mesh, resolution, lower_bound, "
                 "upper_bound).  The occupancy-grid back-end has one (InstantNGPRenderer.render_mesh -> "
-                "pyngp.Testbed.compute_and_save_marching_cubes_mesh); the reference's nerfstudio one is Open3D's Poisson "
-                "reconstruction, which is not built")
+                "pyngp.Testbed.compute_and_save_marching_cubes_mesh).  The reference's nerfstudio one is a point cloud followed by "
+                "Open3D's Poisson reconstruction: the point cloud is built (render_point_cloud -> pointcloud/"
+                "pointcloud_from_nerf.ply, scored by Evaluator3D.calculate_metrics_3d_clouds), the Poisson reconstruction is not")
         voxel_size = 1 / 64
         os.makedirs(f"{self.dir_prediction}/mesh", exist_ok=True)
-        mesh_gt, _ = self.dataset.mesh()
-        points_gt = np.asarray(torch.as_tensor(mesh_gt[0]).detach().cpu().numpy(), dtype=np.float64)
-        lower_gt, upper_gt = points_gt.min(axis=0), points_gt.max(axis=0)
-        corners = np.array([[x, y, z, 1.0] for x in (lower_gt[0], upper_gt[0]) for y in (lower_gt[1], upper_gt[1])
-                            for z in (lower_gt[2], upper_gt[2])])
-        matrix = np.asarray(self.pred2gt_transformation["matrix_pred2gt_scaled"], dtype=np.float64)
-        corners_pred = np.linalg.inv(matrix) @ corners.T  # [4, 8]
-        lower, upper = np.min(corners_pred, axis=1)[:3], np.max(corners_pred, axis=1)[:3]
+        lower_gt, upper_gt, matrix, lower, upper = self._ground_truth_box_in_model_frame()
         resolution = ((upper - lower) * self.pred2gt_transformation["scale_pred2gt"] / voxel_size).astype(int)
         file_raw = f"{self.dir_prediction}/mesh/mesh_from_nerf_raw.ply"
         self.nerf.render_mesh(file_mesh=file_raw, resolution=resolution, lower_bound=lower, upper_bound=upper)
@@ -284,6 +295,41 @@ class EvaluationRenderer:
         file_mesh = f"{self.dir_prediction}/mesh/mesh_from_nerf.ply"
         write_mesh(file_mesh, vertices, faces)
         return file_mesh
+
+    def render_point_cloud(self, num_points: int = 33554432, **kwargs) -> str:
+        """``pointcloud/pointcloud_from_nerf.ply``: the first half of the reference's nerfstudio ``render_mesh``
+        (evaluation/nerf_renderer.py:170-209 there), wrapped the way ``_render_mesh_from_nerf`` wraps the density mesh.  The
+        ground-truth mesh's box is mapped into the model's frame by inv(matrix_pred2gt_scaled); the model's renderer writes
+        its oriented, coloured cloud over the box of the mapped corners to ``pointcloud/pointcloud_from_nerf_raw.ply``
+        (``NerfstudioRenderer.render_point_cloud``; ``kwargs`` go to it); the points are mapped back by
+        ``transform_mesh``'s rule, the normals by the rotation part alone (the linear part divided by ``scale_pred2gt``,
+        float64 row by row, re-normalised), and the cloud cropped to the ground-truth box is written with ``x y z nx ny nz
+        red green blue`` and no faces.  Its own folder, because ``Evaluator3D.calculate_metrics_3d`` reads every
+        ``mesh/*.ply`` as a mesh.  Returns the file's path."""
+        from .meshing import crop_mesh, read_mesh, transform_mesh, write_mesh
+
+        if not callable(getattr(self.nerf, "render_point_cloud", None)):
+            raise NotImplementedError(
+                f"render_point_cloud: {type(self.nerf).__name__} has no render_point_cloud(file_point_cloud, lower_bound, "
+                "upper_bound, num_points).  The nerfstudio back-end has one (NerfstudioRenderer.render_point_cloud); the "
+                "occupancy-grid back-end predicts no normals, and estimating them from neighbours is not built")
+        os.makedirs(f"{self.dir_prediction}/pointcloud", exist_ok=True)
+        lower_gt, upper_gt, matrix, lower, upper = self._ground_truth_box_in_model_frame()
+        file_raw = f"{self.dir_prediction}/pointcloud/pointcloud_from_nerf_raw.ply"
+        self.nerf.render_point_cloud(file_point_cloud=file_raw, lower_bound=lower, upper_bound=upper, num_points=int(num_points),
+                                     **kwargs)
+        points, _, colors, normals = read_mesh(file_raw)
+        if normals is None or colors is None:
+            raise RuntimeError(f"render_point_cloud: {file_raw} has no normals or no colours")
+        no_faces = torch.zeros(0, 3, dtype=torch.int64)
+        points, _, keep = crop_mesh(transform_mesh(points, matrix), no_faces, lower_gt, upper_gt)
+        if points.shape[0] == 0:
+            raise RuntimeError(f"render_point_cloud: nothing of {file_raw} lies inside the ground-truth mesh's box "
+                               f"{lower_gt.tolist()} .. {upper_gt.tolist()}, so pointcloud_from_nerf.ply is not written")
+        normals = rotate_normals(normals[keep], matrix, self.pred2gt_transformation["scale_pred2gt"])
+        file_cloud = f"{self.dir_prediction}/pointcloud/pointcloud_from_nerf.ply"
+        write_mesh(file_cloud, points, no_faces, colors=colors[keep], normals=normals)
+        return file_cloud
 
     def export_keyframe_poses(self) -> np.ndarray:
         """matrices/matrices_origin2frame_keyframes_mapping.json: training poses with the translation in
@@ -330,6 +376,18 @@ class Evaluator2D:
         with open(f"{self.dir_result}/metrics_2d_{folder}.json", "w") as file:
             json.dump(means, file)
         return means
+
+
+def rotate_normals(normals, matrix, scale: float) -> torch.Tensor:
+    """Unit normals under the scaled rigid transform ``matrix`` (4 x 4, linear part = ``scale`` * rotation): mapped by the
+    rotation ``matrix[:3, :3] / scale`` alone, row r as ``(m[r][0]*x + m[r][1]*y) + m[r][2]*z`` in float64 (one product or sum
+    per step, like ``transform_mesh``), re-normalised, float32."""
+    n = torch.as_tensor(normals).to(torch.float64)
+    m = np.asarray(matrix, dtype=np.float64)[:3, :3] / float(scale)
+    x, y, z = n[:, 0], n[:, 1], n[:, 2]
+    rows = [(float(m[r, 0]) * x + float(m[r, 1]) * y) + float(m[r, 2]) * z for r in range(3)]
+    out = torch.stack(rows, dim=1)
+    return (out / torch.linalg.norm(out, dim=1, keepdim=True).clamp_min(1e-300)).to(torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -393,10 +451,25 @@ def calculate_metrics_3d(mesh_gt, mesh_pred, seed: int = 0, device="cuda") -> di
     return metrics_3d_from_clouds(points_gt, points_pred)
 
 
+def calculate_metrics_3d_cloud(mesh_gt, points_pred, seed: int = 0, device="cuda") -> dict:
+    """``calculate_metrics_3d`` for a prediction that already is a cloud (``EvaluationRenderer.render_point_cloud``): the
+    ground-truth cloud as there -- ``NUM_SAMPLE_POINTS_3D`` surface samples from a CPU generator seeded with ``seed``, voxel
+    down-sampled at 1/64 -- the predicted points voxel down-sampled at 1/64 directly, then ``metrics_3d_from_clouds``."""
+    from .pointcloud import sample_points_uniformly, voxel_down_sample
+
+    gen = torch.Generator().manual_seed(int(seed))
+    v = torch.as_tensor(mesh_gt[0]).to(device)
+    points_gt = voxel_down_sample(sample_points_uniformly(v, torch.as_tensor(mesh_gt[1]).to(device), NUM_SAMPLE_POINTS_3D,
+                                                          generator=gen), VOXEL_SIZE_3D)
+    cloud = voxel_down_sample(torch.as_tensor(points_pred).to(device), VOXEL_SIZE_3D)
+    return metrics_3d_from_clouds(points_gt, cloud)
+
+
 class Evaluator3D:
     """``Evaluator.calculate_metrics_3d`` (evaluator.py:148-174): every ``<dir_prediction>/mesh/*.ply`` except
     ``mesh_from_nerf_raw`` against ``dataset.mesh()`` -> ``<dir_result>/metrics_3d.csv`` (the five metrics and ``mesh``,
-    one row per file, files in sorted order)."""
+    one row per file, files in sorted order).  ``calculate_metrics_3d_clouds`` does the same for the point clouds under
+    ``<dir_prediction>/pointcloud`` -> ``metrics_3d_pointcloud.csv``."""
 
     def __init__(self, dataset, dir_prediction: str, dir_result: str, seed: int = 0, device="cuda") -> None:
         self.dataset = dataset
@@ -423,4 +496,27 @@ class Evaluator3D:
         table = pd.DataFrame(rows, columns=list(METRICS_3D) + ["mesh"])
         os.makedirs(self.dir_result, exist_ok=True)
         table.to_csv(f"{self.dir_result}/metrics_3d.csv", index=False)
+        return table[list(METRICS_3D)].squeeze().to_dict()
+
+    def calculate_metrics_3d_clouds(self) -> dict:
+        """Every ``<dir_prediction>/pointcloud/*.ply`` except ``*_raw`` against ``dataset.mesh()`` ->
+        ``<dir_result>/metrics_3d_pointcloud.csv`` with the columns of ``metrics_3d.csv`` (the file's name goes into
+        ``mesh``), one row per file in sorted order (``calculate_metrics_3d_cloud``)."""
+        import pandas as pd
+
+        from .meshing import read_mesh
+
+        mesh_gt, _ = self.dataset.mesh()
+        rows = []
+        for name in sorted(os.listdir(f"{self.dir_prediction}/pointcloud")):
+            stem, ext = os.path.splitext(name)
+            if ext != ".ply" or stem.endswith("_raw"):
+                continue
+            points = read_mesh(f"{self.dir_prediction}/pointcloud/{name}")[0]
+            row = calculate_metrics_3d_cloud(mesh_gt=mesh_gt[:2], points_pred=points, seed=self.seed, device=self.device)
+            row["mesh"] = stem
+            rows.append(row)
+        table = pd.DataFrame(rows, columns=list(METRICS_3D) + ["mesh"])
+        os.makedirs(self.dir_result, exist_ok=True)
+        table.to_csv(f"{self.dir_result}/metrics_3d_pointcloud.csv", index=False)
         return table[list(METRICS_3D)].squeeze().to_dict()

@@ -104,6 +104,135 @@ class NerfstudioRenderer(NeRFRenderer):
         depth = (outputs["depth"] / bundle.metadata["directions_norm"]).cpu().numpy()[..., 0]  # z-depth
         return color, depth
 
+    def render_point_cloud(self, file_point_cloud: str, lower_bound, upper_bound, num_points: int = 33554432,
+                           remove_outliers: bool = True, std_ratio: float = 10.0, min_accumulation: float | None = 0.5,
+                           seed: int = 0) -> dict:
+        """The first half of the reference's ``NerfstudioRenderer.render_mesh`` (evaluation/nerf_renderer.py:170-209
+        there, ``predict_normals=True``): nerfstudio's ``generate_point_cloud`` -- an oriented, coloured cloud of
+        ``num_points`` points back-projected from random training rays inside the box, cleaned by
+        ``remove_statistical_outlier(nb_neighbors=20, std_ratio)`` (pointcloud.py: the k-NN kernel), normals turned
+        towards the cameras -- written to ``file_point_cloud`` as a binary .ply with ``x y z nx ny nz red green blue``
+        and no faces.  The second half, Open3D's Poisson reconstruction of that cloud, is not built.  Returns the cloud
+        (``points``, ``normals``, ``colors``, ``view_directions`` CPU tensors, rows as in the file) and the counts
+        ``generated`` (before the outlier removal) / ``kept``."""
+        from ..meshing import write_mesh
+        from ..pointcloud import remove_statistical_outlier
+
+        if not getattr(self.pipeline.model.config, "predict_normals", False):
+            raise RuntimeError("render_point_cloud: the model was set up with predict_normals=False and has no normals to "
+                               "orient the cloud with -- train with predict_normals=True (the reference's configuration)")
+        cloud = generate_point_cloud(self.pipeline, self.matrices_origin2frame_training, lower_bound, upper_bound,
+                                     num_points=num_points, min_accumulation=min_accumulation, seed=seed)
+        points, normals, colors, views = cloud["points"], cloud["normals"], cloud["colors"], cloud["view_directions"]
+        generated = int(points.shape[0])
+        if remove_outliers:
+            points, index = remove_statistical_outlier(points, nb_neighbors=20, std_ratio=std_ratio)
+            normals, colors, views = normals[index], colors[index], views[index]
+        normals = orient_normals_towards_cameras(normals, views)
+        out = {"points": points.cpu(), "normals": normals.cpu(), "colors": colors.cpu(), "view_directions": views.cpu(),
+               "generated": generated, "kept": int(points.shape[0])}
+        write_mesh(file_point_cloud, out["points"], torch.zeros(0, 3, dtype=torch.int64), colors=out["colors"],
+                   normals=out["normals"])
+        return out
+
+
+# generate_point_cloud gives up after this many consecutive batches without a single kept point
+POINT_CLOUD_EMPTY_BATCHES = 8
+# ... and, from that many batches on, when fewer than one ray in this many is kept (the run would not end in reasonable time)
+POINT_CLOUD_MIN_SHARE = 1024
+POINT_CLOUD_RAYS_PER_BATCH = 1 << 20
+
+
+def orient_normals_towards_cameras(normals: torch.Tensor, view_directions: torch.Tensor) -> torch.Tensor:
+    """A normal with ``dot(view_direction, normal) > 0`` (it points along the ray, away from the camera that saw the
+    point) is negated [UPSTREAM nerfstudio generate_point_cloud, not vendored]."""
+    away = (view_directions * normals).sum(dim=-1) > 0
+    return torch.where(away[:, None], -normals, normals)
+
+
+@torch.no_grad()
+def generate_point_cloud(pipeline, matrices_origin2frame, lower_bound, upper_bound, num_points: int = 33554432,
+                         min_accumulation: float | None = 0.5, seed: int = 0, rays_per_batch: int | None = None) -> dict:
+    """nerfstudio's ``generate_point_cloud`` over the native engine [UPSTREAM: exporter_utils.py, not vendored in the
+    reference tree -- the rule below is restated from its documented behaviour and cannot be verified here; that covers
+    ``min_accumulation``, which newer upstream versions apply as ``accumulation > 0.5`` and older ones do not have:
+    ``None`` switches it off].
+
+    Rays: random pixels ``floor(rand(R, 3) * [n_active, H, W])`` of the active training frames
+    (``DynamicDataManager.sample_pixels``'s rule) from a generator of its own seeded with ``seed`` -- the training stream
+    does not advance -- through cameras at ``matrices_origin2frame`` ([n, 4, 4] or [n, 3, 4]: the camera-optimiser-corrected
+    training poses).  Every batch has ``rays_per_batch`` rays (default: ``min(2^20, max(4096, num_points rounded up to a power
+    of two))``) and goes through ``NerfactoEngine.render_image(normals=True)``: one captured graph serves the whole run.
+    Per ray: ``point = origin + direction * depth`` per component in float32, with the bundle's ``directions`` (UNIT
+    vectors: the ray generator normalises them and reports the norm separately) and the model's ``depth`` output (the
+    distance along that unit direction, not the z-depth); ``rgb`` as uint8 by the renderer's rule (``rgb * 255``,
+    truncated); ``normal = 2 n - 1`` of the engine's ``normals`` output, which is in (n + 1) / 2 colour space,
+    re-normalised.  A point is kept when ``accumulation > min_accumulation`` and ``lower < point < upper`` strictly on
+    every axis.  Batches are appended in order until ``num_points`` are kept, the last one cut to fit.
+    ``POINT_CLOUD_EMPTY_BATCHES`` consecutive batches without a kept point raise, and so does a share of kept rays below
+    1 in ``POINT_CLOUD_MIN_SHARE`` from that many batches on: the loop ends.  Returns GPU tensors ``points``,
+    ``normals``, ``view_directions`` (float32 [K, 3]), ``colors`` (uint8 [K, 3])."""
+    from .cameras import Cameras, CameraType
+
+    num_points = int(num_points)
+    if num_points < 1:
+        raise ValueError("generate_point_cloud: num_points must be positive")
+    model = pipeline.model
+    eng = model.engine
+    dev = torch.device(pipeline.device)
+    ds = pipeline.datamanager.train_dataset
+    n_active = int(ds.num_active_frames)
+    poses = np.asarray(matrices_origin2frame, dtype=np.float64)[:n_active, :3, :4]
+    if poses.shape[0] != n_active or n_active < 1:
+        raise ValueError(f"generate_point_cloud: {poses.shape[0]} poses for {n_active} active training frames")
+    src = ds.cameras
+    cameras = Cameras(camera_to_worlds=torch.tensor(poses, dtype=torch.float32, device=dev), fx=src.fx.to(dev), fy=src.fy.to(dev),
+                      cx=src.cx.to(dev), cy=src.cy.to(dev), width=src.width, height=src.height, camera_type=CameraType.PERSPECTIVE)
+    if rays_per_batch is None:
+        rays_per_batch = min(POINT_CLOUD_RAYS_PER_BATCH, max(4096, 1 << (num_points - 1).bit_length()))
+    rays_per_batch = int(rays_per_batch)
+    chunk = int(model.config.eval_num_rays_per_chunk)
+    lower = torch.as_tensor(np.asarray(lower_bound, dtype=np.float64).reshape(3)).to(dev, torch.float32)
+    upper = torch.as_tensor(np.asarray(upper_bound, dtype=np.float64).reshape(3)).to(dev, torch.float32)
+    generator = torch.Generator(device=dev)
+    generator.manual_seed(int(seed))
+    scale = torch.tensor([n_active, int(ds.frame_height), int(ds.frame_width)], device=dev)
+    parts = {"points": [], "normals": [], "view_directions": [], "colors": []}
+    kept_total, rays_total, empty = 0, 0, 0
+    while kept_total < num_points:
+        pixels = torch.floor(torch.rand((rays_per_batch, 3), device=dev, generator=generator) * scale).long()
+        bundle = cameras.generate_rays(camera_indices=pixels)
+        origins, directions = bundle.origins.reshape(-1, 3), bundle.directions.reshape(-1, 3)
+        out = eng.render_image(origins, directions, bundle.metadata["directions_norm"].reshape(-1), normals=True, chunk=chunk)
+        points = origins + directions * out["depth"]
+        keep = ((points > lower) & (points < upper)).all(dim=1)
+        if min_accumulation is not None:
+            keep &= out["accumulation"][:, 0] > float(min_accumulation)
+        index = keep.nonzero().flatten()[:num_points - kept_total]
+        rays_total += rays_per_batch
+        if index.numel() == 0:
+            empty += 1
+            if empty >= POINT_CLOUD_EMPTY_BATCHES:
+                raise RuntimeError(
+                    f"generate_point_cloud: {empty} consecutive batches of {rays_per_batch} rays left no point inside the box "
+                    f"{lower.tolist()} .. {upper.tolist()}" + ("" if min_accumulation is None else f" with accumulation > {min_accumulation}")
+                    + f"; {kept_total} of {rays_total} rays ({kept_total / rays_total:.3%}) were kept so far -- the field is empty "
+                    "there (train longer), or the box is not in the model's frame")
+            continue
+        empty = 0
+        if rays_total >= POINT_CLOUD_EMPTY_BATCHES * rays_per_batch and (kept_total + int(index.numel())) * POINT_CLOUD_MIN_SHARE < rays_total:
+            raise RuntimeError(
+                f"generate_point_cloud: only {kept_total + int(index.numel())} of {rays_total} rays gave a point inside the box "
+                f"{lower.tolist()} .. {upper.tolist()} (fewer than 1 in {POINT_CLOUD_MIN_SHARE}): {num_points} points would take "
+                "too long -- check the box, or ask for fewer points")
+        normal = 2.0 * out["normals"][index] - 1.0
+        parts["points"].append(points[index])
+        parts["normals"].append(normal / torch.linalg.norm(normal, dim=1, keepdim=True).clamp_min(1e-20))
+        parts["view_directions"].append(directions[index])
+        parts["colors"].append((out["rgb"][index] * 255).to(torch.uint8))  # truncation, like render_frame
+        kept_total += int(index.numel())
+    return {k: torch.cat(v) for k, v in parts.items()}
+
 
 def calculate_psnr_reference(image1: np.ndarray, image2: np.ndarray) -> float:
     """Bit-faithful to the reference: the subtraction and the square are evaluated in uint8 and wrap

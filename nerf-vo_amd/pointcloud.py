@@ -15,6 +15,11 @@ library is not available where this project is built and tested.  They follow Op
 drawn by area and square-root barycentrics; mean of the points per voxel of the lattice floor(p / voxel_size);
 point-to-point ICP with Kabsch updates and the relative fitness / RMSE criteria) and are tested against this project's
 own float64 restatements.
+
+The point cloud of the nerfstudio back-end (mapping/renderer.py: ``render_point_cloud``) adds the k-nearest-neighbour search
+on the same grid (csrc/knn.hip: ``nvo_knn_query`` behind ``NeighbourGrid.query_knn``, bit for bit the brute force of
+tests/helpers/knn_oracle.py) and ``remove_statistical_outlier`` on it, which follows Open3D's
+documented rule; its parity with Open3D is UNPINNED for the same reason.
 """
 from __future__ import annotations
 
@@ -139,6 +144,120 @@ class NeighbourGrid:
         dist2[perm] = d2s
         index[perm] = idxs.long()
         return dist2, index
+
+    @torch.no_grad()
+    def query_knn(self, queries, k: int, want: str = "table"):
+        """The ``k`` nearest target points of each query (csrc/knn.hip: ``nvo_knn_query``; DESIGN.md "k nearest neighbours
+        and the point cloud"), ``1 <= k <= 32``.  ``want='table'`` -> ``(dist2 float32 [N, k], index int64 [N, k])``: the
+        k smallest pairs (squared distance ``(dx*dx + dy*dy) + dz*dz`` in float32, index into the points the grid was built
+        from) in ascending lexicographic order, ties on the distance going to the smaller index; with fewer than ``k``
+        target points the remaining slots hold ``inf`` and ``-1``.  A cloud that queries itself finds each point at distance
+        0.  ``want='mean'`` -> float32 [N]: the mean of the ``min(k, M)`` distances (not squared), summed in that order in
+        float32, without the table ever being written.  With ``k = 1`` the table is ``query``'s result."""
+        if want not in ("table", "mean"):
+            raise ValueError(f"NeighbourGrid.query_knn: want must be 'table' or 'mean', got {want!r}")
+        k = int(k)
+        if not 1 <= k <= _lib.KNN_MAX_K:
+            raise ValueError(f"NeighbourGrid.query_knn: k = {k} must be between 1 and {_lib.KNN_MAX_K}")
+        q = torch.as_tensor(queries)
+        if not (q.is_cuda and self.points.is_cuda):
+            raise RuntimeError("NeighbourGrid.query_knn: the grid and the queries must be on the GPU -- no CPU fallback")
+        q = _as_points(q, "NeighbourGrid.query_knn").to(self.device)
+        if q.shape[0] >= 2 ** 31:
+            raise ValueError("NeighbourGrid.query_knn: at most 2^31 - 1 queries")
+        # queries sorted by their own cell, as in query (any order gives the same result)
+        perm = torch.argsort(self.cells_of(q))
+        qs = q[perm].contiguous()
+        n = int(q.shape[0])
+        d2s = idxs = means = None
+        if want == "table":
+            d2s = torch.empty(n, k, dtype=torch.float32, device=self.device)
+            idxs = torch.empty(n, k, dtype=torch.int32, device=self.device)
+        else:
+            means = torch.empty(n, dtype=torch.float32, device=self.device)
+        args = _lib.KnnArgs(
+            points=self.points.data_ptr(), point_index=self.point_index.data_ptr(), cell_start=self.cell_start.data_ptr(),
+            queries=qs.data_ptr(), out_dist2=None if d2s is None else d2s.data_ptr(),
+            out_index=None if idxs is None else idxs.data_ptr(), out_mean_dist=None if means is None else means.data_ptr(),
+            N=n, M=self.n_points, k=k, gx=self.dims[0], gy=self.dims[1], gz=self.dims[2], lower_x=self.lower[0],
+            lower_y=self.lower[1], lower_z=self.lower[2], cell_size=self.cell_size)
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(_lib.lib().nvo_knn_query(stream, C.byref(args)), "knn_query")
+        if want == "mean":
+            out = torch.empty_like(means)
+            out[perm] = means
+            return out
+        dist2 = torch.empty_like(d2s)
+        index = torch.empty(n, k, dtype=torch.int64, device=self.device)
+        dist2[perm] = d2s
+        index[perm] = idxs.long()
+        return dist2, index
+
+
+# Cell size of the self-query behind remove_statistical_outlier: cells that hold about KNN_POINTS_PER_CELL_FACTOR * k points
+# of a SURFACE-like cloud, whose area is taken as that of its bounding box.  0.25 (five points per cell at k = 20) is the
+# fastest setting of tools/knn_bench.py at 2 * 10^5 and 2 * 10^6 surface points (table in EXPERIMENTS.md section 17); at
+# 3.4 * 10^7 points over a room the caps of the grid decide the cell size, and the smallest allowed one is the fastest.
+KNN_POINTS_PER_CELL_FACTOR = 0.25
+
+
+def knn_cell_size(n_points: int, extent, k: int, factor: float = KNN_POINTS_PER_CELL_FACTOR, max_cells: int = MAX_CELLS) -> float:
+    """``sqrt(factor * k * area / n_points)`` with ``area`` the surface of the ``extent`` box (its two largest sides when
+    one side is zero, its longest side squared when two are), raised where needed so that the grid keeps to
+    ``NN_MAX_CELLS_PER_AXIS`` cells per axis and ``max_cells`` cells."""
+    e = [max(float(v), 0.0) for v in extent]
+    area = 2.0 * (e[0] * e[1] + e[1] * e[2] + e[0] * e[2])
+    if not area > 0:
+        area = max(max(e) ** 2, 1e-12)
+    cell = math.sqrt(float(factor) * int(k) * area / max(int(n_points), 1))
+    floor_axis = max(e) / (_lib.NN_MAX_CELLS_PER_AXIS - 2)
+    floor_cells = (max(e[0], cell) * max(e[1], cell) * max(e[2], cell) / (0.5 * min(int(max_cells), 2 ** 31 - 1))) ** (1 / 3)
+    return max(cell, floor_axis, floor_cells, 1e-9)
+
+
+def statistical_outlier_mask(avg: torch.Tensor, std_ratio: float):
+    """The rule of ``remove_statistical_outlier`` on the mean neighbour distances ``avg`` [N] -> ``(keep bool [N],
+    threshold)``: with ``a = avg`` as float64 and V the points with ``a > 0``, ``mean = sum_V a / |V|``,
+    ``std = sqrt(sum_V (a - mean)^2 / (|V| - 1))``, ``threshold = mean + std_ratio * std``; a point is kept when
+    ``0 < a < threshold``.  Any device."""
+    a = torch.as_tensor(avg).to(torch.float64)
+    valid = a > 0
+    n_valid = int(valid.sum())
+    if n_valid < 2:
+        raise ValueError(f"remove_statistical_outlier: {n_valid} of {a.shape[0]} points have a positive mean neighbour "
+                         "distance; the standard deviation needs at least 2 (are all points duplicates of one another?)")
+    av = a[valid]
+    mean = float(av.sum()) / n_valid
+    std = math.sqrt(float(((av - mean) ** 2).sum()) / (n_valid - 1))
+    threshold = mean + float(std_ratio) * std
+    return valid & (a < threshold), threshold
+
+
+@torch.no_grad()
+def remove_statistical_outlier(points, nb_neighbors: int = 20, std_ratio: float = 10.0, cell_size=None):
+    """Open3D's ``PointCloud.remove_statistical_outlier`` as documented (parity with Open3D is UNPINNED: the library is
+    not available where this project is built and tested) -> ``(kept_points float32 [K, 3], kept_index int64 [K])`` in
+    input order, for points on the GPU (no CPU fallback: the search is ``NeighbourGrid.query_knn(want='mean')``).
+    ``avg[i]`` = the float32 mean distance of point i to its ``nb_neighbors`` nearest points of the cloud itself, the
+    point included at distance 0; the rule on it is ``statistical_outlier_mask``.  ``cell_size``: of the search grid, by
+    default ``knn_cell_size`` of the cloud; the result does not depend on it."""
+    pts = torch.as_tensor(points)
+    if not pts.is_cuda:
+        raise RuntimeError("remove_statistical_outlier: the points must be on the GPU -- no CPU fallback")
+    pts = _as_points(pts, "remove_statistical_outlier")
+    nb = int(nb_neighbors)
+    if not 1 <= nb <= _lib.KNN_MAX_K:
+        raise ValueError(f"remove_statistical_outlier: nb_neighbors = {nb} must be between 1 and {_lib.KNN_MAX_K}")
+    if not float(std_ratio) > 0:
+        raise ValueError("remove_statistical_outlier: std_ratio must be positive")
+    if cell_size is None:
+        extent = (pts.max(dim=0).values - pts.min(dim=0).values).tolist()
+        cell_size = knn_cell_size(pts.shape[0], extent, nb)
+    avg = NeighbourGrid(pts, cell_size).query_knn(pts, nb, want="mean")
+    keep, _ = statistical_outlier_mask(avg, std_ratio)
+    index = keep.nonzero().flatten()
+    return pts[index], index
 
 
 def sample_points_uniformly(vertices, faces, number_of_points: int, generator=None) -> torch.Tensor:

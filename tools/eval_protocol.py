@@ -106,12 +106,14 @@ def _log(mapper):
 def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, eval_frames=8, chunk=8, device="cuda:0",
         camera_optimizer_mode=None, pose_noise=None, deterministic=False, seed=42, dynamic_loss_scale=None, out_dir=None,
         quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None, mesh=False, metrics_3d=False,
-        mesh_nerf=False):
+        mesh_nerf=False, pointcloud=False, pointcloud_points=33554432):
     """``method``: 'nerfstudio' (the default mapper) or 'instant-ngp' (the occupancy-grid back-end through the pyngp facade,
     /root/reference/nerf_vo/mapping/instant_ngp.py + evaluation/nerf_renderer.py:221-320; the room is shrunk by
     ``scene_scale``, default 0.5, so that it lies inside that back-end's scene box: it takes poses as they come).
     ``mesh_nerf`` (instant-ngp only): also ``render_mesh(source='nerf')``, the density iso-surface cropped to the ground-truth
-    mesh's box (run.py:72); with ``metrics_3d`` the table gains its row."""
+    mesh's box (run.py:72); with ``metrics_3d`` the table gains its row.
+    ``pointcloud`` (nerfstudio only): also ``render_point_cloud(num_points=pointcloud_points)`` -- the oriented, coloured cloud
+    of the field, outliers removed, cropped to the ground-truth mesh's box -- and its score, results/metrics_3d_pointcloud.csv."""
     entry.build()
     from nerf_vo_amd.evaluation import (EvaluationRenderer, Evaluator2D, Evaluator3D, read_color, transform_matrices_pred2gt)
     from nerf_vo_amd.mapping.dataset import opencv_to_opengl
@@ -127,6 +129,8 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
     ngp = method == "instant-ngp"
     if mesh_nerf and not ngp:
         raise SystemExit("--mesh-nerf needs --method instant-ngp (the nerfstudio back-end has no density mesh)")
+    if pointcloud and ngp:
+        raise SystemExit("--pointcloud needs --method nerfstudio (the occupancy-grid back-end predicts no normals)")
     if ngp and abs(width / height - 1200.0 / 680.0) > 0.01:
         # (the testbed's free camera has ONE focal length, evaluation/nerf_renderer.py:152: Replica's intrinsics have square
         # pixels only at its own aspect -- 160 x 120 renders with fx != fy come out at 13 dB)
@@ -195,6 +199,20 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
         file_mesh = renderer.render_mesh(source="nerf")
         mesh_nerf_info = {"file": file_mesh if not own_dir else os.path.basename(file_mesh), "bytes": os.path.getsize(file_mesh),
                           "seconds": time.perf_counter() - t_mesh}
+    cloud_info = None
+    if pointcloud:  # the first half of the reference's nerfstudio render_mesh: pointcloud/pointcloud_from_nerf.ply, and its score
+        import pandas as pd
+
+        t_cloud = time.perf_counter()
+        file_cloud = renderer.render_point_cloud(num_points=int(pointcloud_points))
+        seconds_cloud = time.perf_counter() - t_cloud
+        t_cloud = time.perf_counter()
+        Evaluator3D(ds, args.dir_prediction, out_dir + "/results").calculate_metrics_3d_clouds()
+        row = pd.read_csv(out_dir + "/results/metrics_3d_pointcloud.csv").set_index("mesh").loc["pointcloud_from_nerf"]
+        cloud_info = {"file": file_cloud if not own_dir else os.path.basename(file_cloud), "bytes": os.path.getsize(file_cloud),
+                      "points_requested": int(pointcloud_points), "seconds": seconds_cloud,
+                      "metrics_3d": {k: float(v) for k, v in row.items()},
+                      "metrics_seconds_incl_ground_truth_mesh": time.perf_counter() - t_cloud}
     m_3d = None
     if metrics_3d:  # run.py:79: ground-truth mesh fused from all ground-truth frames, results/metrics_3d.csv
         import pandas as pd
@@ -243,6 +261,8 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
         res["mesh_nerf"] = mesh_nerf_info
     if m_3d is not None:
         res["metrics_3d"] = m_3d
+    if cloud_info is not None:
+        res["pointcloud"] = cloud_info
     if ngp:
         res.update({"camera_optimizer_mode": "instant-ngp extrinsics", "ms_per_step_incl_ingest": 1e3 * train_s / iterations,
                     "rays_per_batch": eng.rays_per_batch, "applied_steps": eng.applied_steps})
@@ -276,8 +296,13 @@ if __name__ == "__main__":
                     "(results/metrics_3d.csv); implies --mesh")
     ap.add_argument("--mesh-nerf", action="store_true", help="instant-ngp only: also extract the density iso-surface, cropped to "
                     "the ground-truth mesh's box (mesh/mesh_from_nerf.ply); with --metrics-3d the table gains its row")
+    ap.add_argument("--pointcloud", action="store_true", help="nerfstudio only: also export the field's oriented point cloud, "
+                    "cropped to the ground-truth mesh's box (pointcloud/pointcloud_from_nerf.ply), and score it "
+                    "(results/metrics_3d_pointcloud.csv)")
+    ap.add_argument("--pointcloud-points", type=int, default=33554432, help="points of the cloud before outlier removal and crop")
     a = ap.parse_args()
     run(a.keyframes, a.height, a.width, a.iterations, eval_frames=a.eval_frames, camera_optimizer_mode=a.camera_optimizer_mode,
         pose_noise=a.pose_noise, deterministic=a.deterministic, seed=a.seed, quiet=False,
         dynamic_loss_scale=False if a.static_loss_scale else None, keyframe_views=not a.no_keyframe_views,
-        method=a.method, scene_scale=a.scene_scale, mesh=a.mesh, metrics_3d=a.metrics_3d, mesh_nerf=a.mesh_nerf)
+        method=a.method, scene_scale=a.scene_scale, mesh=a.mesh, metrics_3d=a.metrics_3d, mesh_nerf=a.mesh_nerf,
+        pointcloud=a.pointcloud, pointcloud_points=a.pointcloud_points)
