@@ -649,10 +649,12 @@ typedef struct nvo_ngp_loss_args {
     float* losses;               /* [64][8] shards: slot 0 rgb, slot 1 depth */
     void* d_rgb_out;             /* fp16 [capacity][d_rgb_stride]; NULL -> inference */
     uint32_t d_rgb_stride;
-    float* d_density_pre;        /* [capacity] */
+    float* d_density_pre;        /* [capacity]; exact 0 on a sample whose optical step exp(pre) dt is capped at 128 */
     /* inference in rounds (nvo_occ_march_resume): the optical depth the ray has gathered in earlier rounds (NULL: none),
      * where to leave the total (nullable), and whether out_rgb / out_depth / out_accumulation are ADDED to (a later round)
-     * or overwritten.  Training ignores the three. */
+     * or overwritten.  Training ignores the three.  Inference with any of the three set requires background == NULL (the
+     * call is refused otherwise): every round adds T_final * background, and a ray that sits a later round out (count 0)
+     * would add it once more -- the caller blends the background once, behind the last round. */
     const float* carry_in;       /* [R] */
     float* carry_out;            /* [R] */
     uint32_t accumulate_outputs;

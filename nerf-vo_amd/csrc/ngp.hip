@@ -212,7 +212,7 @@ k_ngp_composite_loss(nvo_ngp_loss_args a, uint32_t ray_blocks) {
             const float suffix = total_q - incl_q;
             const bool dead = T < a.train_min_transmittance;
             const float dsigma = dts * (T * __expf(-dd) * dot - suffix - g_bg);
-            a.d_density_pre[s] = dead ? 0.f : dsigma * fminf(sigma, 3.2690173e6f) * a.loss_scale;
+            a.d_density_pre[s] = (dead || !(dd < 128.f)) ? 0.f : dsigma * fminf(sigma, 3.2690173e6f) * a.loss_scale;
             _Float16* d_rgb = (_Float16*)a.d_rgb_out;
 #pragma unroll
             for (int k = 0; k < 3; ++k)
@@ -361,8 +361,12 @@ k_ngp_composite_loss(nvo_ngp_loss_args a, uint32_t ray_blocks) {
             // there): exact zeros, which the backwards behind this kernel skip
             const bool dead = T < a.train_min_transmittance;
             const float dsigma = a.dt[s] * (T * __expf(-dd) * dot - suffix - g_bg);
-            // density = exp(x): dsigma/dx = sigma (clamped like tcnn's Exponential activation backward)
-            a.d_density_pre[s] = dead ? 0.f : dsigma * fminf(sigma, 3.2690173e6f) * a.loss_scale;
+            // density = exp(x): dsigma/dx = sigma (clamped like tcnn's Exponential activation backward).  A sample whose
+            // optical step is capped gets an exact zero, the derivative of min(., 128): its bracket is below exp(-128) in
+            // exact arithmetic, but `suffix` is the difference of two float32 sums of all q -- rounding noise of about
+            // 1e-7 |total_q| -- and the clamped sigma of a capped sample (3.27e6) turned that noise into a gradient of
+            // several per cent of the ray's largest true one (EXPERIMENTS.md section 18)
+            a.d_density_pre[s] = (dead || !(dd < 128.f)) ? 0.f : dsigma * fminf(sigma, 3.2690173e6f) * a.loss_scale;
 #pragma unroll
             for (int k = 0; k < 3; ++k)  // rgb = sigmoid(y): drgb/dy = rgb (1 - rgb)
                 d_rgb[s * a.d_rgb_stride + k] = dead ? (_Float16)0.f : (_Float16)(w * g_pix[k] * rgb[k] * (1.f - rgb[k]) * a.loss_scale);
@@ -518,6 +522,9 @@ int nvo_ngp_composite_loss(nvo_stream_t stream, const nvo_ngp_loss_args* args) {
     NVO_REQUIRE(a.counts && a.offsets && a.t && a.dt && a.density_out && a.rgb_out, "ngp_composite_loss: NULL input");
     NVO_REQUIRE(!a.d_rgb_out || (a.d_density_pre && a.gt_rgb && a.losses && a.ray_idx && a.d_rgb_stride >= 3),
                 "ngp_composite_loss: training mode needs d_density_pre, gt_rgb, losses, ray_idx");
+    // (a ray that sits a later round out -- count 0 -- would add T * background once more)
+    NVO_REQUIRE(a.d_rgb_out || !a.background || !(a.carry_in || a.carry_out || a.accumulate_outputs),
+                "ngp_composite_loss: inference in rounds (carry_in / carry_out / accumulate_outputs) needs background == NULL");
     if (a.R == 0) return NVO_OK;
     hipStream_t s = (hipStream_t)stream;
     NVO_PROF(stream, "ngp_composite_loss");
