@@ -6,6 +6,7 @@
 // 2.4 K8/K12, reference call sites /root/reference/nerf_vo/mapping/nerfstudio_utils.py:286-300.
 // CPU restatement: oracle/rays.py.
 #include "nvo_kernels.h"
+#include <stdlib.h>
 #include <string.h>
 #include "../../include/nerfvo_hip.h"
 
@@ -249,12 +250,43 @@ k_sample_pixels(uint32_t R, uint32_t seed, const float* __restrict__ step_dev, c
 
 // The whole per-ray prefix of a training step in ONE launch: pixel sampler + sampler jitters (k_sample_pixels), ray
 // generation with pose correction (k_raygen), target gather + direction-encoding input (k_gather_targets), SH(4) of
-// the direction (k_sh_fwd) and the first sampler level (k_lindisp_positions).  Thread per (ray, sample of level 0):
-// every thread re-derives its ray (a hash and ~80 flops -- free next to the five launches it replaces, ~6 us each of
-// dispatch + drain for 4096-ray kernels); the thread of sample 0 writes the per-ray outputs.  Same device functions
-// as the separate kernels: the results are bit-identical (tests/test_engine_gpu.py::test_ray_head_matches_separate).
-// Workgroups behind the ray blocks (zero.n != 0: nvo_ray_head_zero) clear the step's accumulate-into buffers: the first
-// launch of a one-graph step does both, a 5 us launch less in front of the main field's forward.
+// the direction (k_sh_fwd) and the first sampler level (k_lindisp_positions).  Same device functions on the same
+// inputs as the separate kernels: the results are bit-identical (tests/test_engine_gpu.py::
+// test_ray_head_matches_separate, tests/test_ray_head_forms_gpu.py).  Extra workgroups (zero.n != 0: nvo_ray_head_zero)
+// clear the step's accumulate-into buffers: the first launch of a one-graph step does both, a 5 us launch less in
+// front of the main field's forward.
+//
+// Two forms, chosen by ray_head_launch:
+//  * k_ray_head_x4 -- S % 4 == 0, R * S < 2^32 / 12, x01 and the SH rows 16-byte aligned (every shape the engine runs).
+//    A thread owns FOUR consecutive samples of one ray: five bin edges computed once each (the thread-per-sample form
+//    computes every edge twice), x01 leaves as three 16-byte stores.  A workgroup covers 1024 samples -- 4 rays at
+//    S = 256 -- so 4096 x 256 samples are 1024 workgroups, all resident at once.  The first lanes derive the
+//    workgroup's rays into LDS once and write the per-ray outputs themselves (SH row: two 16-byte stores); meanwhile
+//    every thread computes and stores its bins, which need the ray's jitter hash alone; behind an LDS-only barrier the
+//    positions follow.  Bin rows as plain dword stores and the zero-plan workgroups LAST in the grid: the wider /
+//    earlier alternatives measured no better (EXPERIMENTS.md 12.6).
+//  * k_ray_head -- thread per (ray, sample), any S and alignment; NVO_RAY_HEAD_GENERIC=1 forces it (tests, A/B).
+struct HeadRay {
+    int32_t idx[3];
+    float jit0, o[3], d[3], n0, area;
+};
+
+// pixel sampler + first jitter + ray generation of ray r (k_sample_pixels, k_raygen)
+__device__ __forceinline__ void head_ray_derive(const nvo_ray_head_args& a, uint32_t step, uint32_t r, HeadRay& h) {
+    int64_t idx[3];
+#pragma unroll
+    for (uint32_t c = 0; c < 3; ++c) {
+        const float e = a.extent_dev[c];
+        const float v = floorf(hash_uniform(a.seed, step, c, r) * e);
+        idx[c] = (int64_t)fminf(v, e - 1.f);
+        h.idx[c] = (int32_t)idx[c];
+    }
+    h.jit0 = hash_uniform(a.seed, step, 3u, r);
+    const int64_t cam = idx[0];
+    raygen_one((float)idx[2] + 0.5f, (float)idx[1] + 0.5f, a.intrinsics + 4 * cam, a.c2w + (size_t)a.c2w_stride * cam,
+               a.corrections ? a.corrections + 12 * cam : nullptr, h.o, h.d, &h.n0, &h.area);
+}
+
 __global__ void __launch_bounds__(256)
 k_ray_head(nvo_ray_head_args a, NvoZeroPlan zero, uint32_t ray_blocks) {
     if (blockIdx.x >= ray_blocks) {  // (uniform)
@@ -266,10 +298,6 @@ k_ray_head(nvo_ray_head_args a, NvoZeroPlan zero, uint32_t ray_blocks) {
     // (18.7 -> 17.4 us: most of the launch is its 25-31 MB of stores and the zero plan).  Same
     // device functions on the same inputs: the values do not change.
     constexpr uint32_t kHeadRays = 8;
-    struct HeadRay {
-        int32_t idx[3];
-        float jit0, o[3], d[3], n0, area;
-    };
     __shared__ HeadRay s_ray[kHeadRays];
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t total = a.R * a.S;
@@ -278,20 +306,7 @@ k_ray_head(nvo_ray_head_args a, NvoZeroPlan zero, uint32_t ray_blocks) {
     const uint32_t r_first = i_first / a.S, n_rays = i_last / a.S - r_first + 1u;
     const bool shared_rays = n_rays <= kHeadRays;  // (uniform)
     const uint32_t step = (uint32_t)a.step_dev[0];
-    auto derive = [&](uint32_t r, HeadRay& h) {
-        int64_t idx[3];
-#pragma unroll
-        for (uint32_t c = 0; c < 3; ++c) {
-            const float e = a.extent_dev[c];
-            const float v = floorf(hash_uniform(a.seed, step, c, r) * e);
-            idx[c] = (int64_t)fminf(v, e - 1.f);
-            h.idx[c] = (int32_t)idx[c];
-        }
-        h.jit0 = hash_uniform(a.seed, step, 3u, r);
-        const int64_t cam = idx[0];
-        raygen_one((float)idx[2] + 0.5f, (float)idx[1] + 0.5f, a.intrinsics + 4 * cam, a.c2w + (size_t)a.c2w_stride * cam,
-                   a.corrections ? a.corrections + 12 * cam : nullptr, h.o, h.d, &h.n0, &h.area);
-    };
+    auto derive = [&](uint32_t r, HeadRay& h) { head_ray_derive(a, step, r, h); };
     if (shared_rays) {
         if (threadIdx.x < n_rays) derive(r_first + threadIdx.x, s_ray[threadIdx.x]);
         __syncthreads();
@@ -354,6 +369,135 @@ k_ray_head(nvo_ray_head_args a, NvoZeroPlan zero, uint32_t ray_blocks) {
 #pragma unroll
         for (int k = 0; k < 16; ++k) sp[k] = nvo_cvt16(c[k], a.sh_bf16 != 0);
     }
+}
+
+// ---- the 4-samples-per-thread form -------------------------------------------------------------------------------
+struct HeadTargets {
+    float rgb[3], depth, normal[3];
+};
+
+// the target gather of one ray (k_gather_targets): all seven loads in front of the first store
+__device__ __forceinline__ void head_ray_gather(const nvo_ray_head_args& a, const HeadRay& h, HeadTargets& t) {
+    const size_t pix = ((size_t)h.idx[0] * a.H + (size_t)h.idx[1]) * a.W + (size_t)h.idx[2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t.rgb[k] = a.images[3 * pix + k];
+    t.depth = a.depths ? a.depths[pix] : 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t.normal[k] = a.normals ? a.normals[3 * pix + k] : 0.f;
+}
+
+// every per-ray output of ray r (a.sh is 16-byte aligned: ray_head_launch)
+__device__ __forceinline__ void head_ray_store(const nvo_ray_head_args& a, uint32_t step, uint32_t r, const HeadRay& h,
+                                               const HeadTargets& t) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a.ray_indices[3 * (size_t)r + k] = (int64_t)h.idx[k];
+        a.origins[3 * (size_t)r + k] = h.o[k];
+        a.directions[3 * (size_t)r + k] = h.d[k];
+    }
+    a.jitter[r] = h.jit0;
+    for (uint32_t q = 1; q < a.n_jitter; ++q) a.jitter[(size_t)q * a.R + r] = hash_uniform(a.seed, step, 3u + q, r);
+    a.directions_norm[r] = h.n0;
+    if (a.pixel_area) a.pixel_area[r] = h.area;
+    a.cam_idx[r] = h.idx[0];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.gt_rgb[3 * (size_t)r + k] = t.rgb[k];
+    if (a.depths) a.gt_depth[r] = t.depth;
+    if (a.normals) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a.gt_normal[3 * (size_t)r + k] = t.normal[k];
+    }
+    float d01[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        d01[k] = (h.d[k] + 1.f) * 0.5f;
+        a.dirs01[3 * (size_t)r + k] = d01[k];
+    }
+    if (a.sh) {  // k_sh_fwd on (d + 1) / 2, degree 4: the row's 16 halves as two 16-byte stores
+        float c[16];
+        nvo_sh4_eval(d01[0] * 2.f - 1.f, d01[1] * 2.f - 1.f, d01[2] * 2.f - 1.f, 4u, c);
+        const bool bf = a.sh_bf16 != 0;
+        uint4* __restrict__ sp = reinterpret_cast<uint4*>((nvo_h16*)a.sh + 16 * (size_t)r);
+        sp[0] = make_uint4(nvo_cvt16x2(c[0], c[1], bf), nvo_cvt16x2(c[2], c[3], bf), nvo_cvt16x2(c[4], c[5], bf),
+                           nvo_cvt16x2(c[6], c[7], bf));
+        sp[1] = make_uint4(nvo_cvt16x2(c[8], c[9], bf), nvo_cvt16x2(c[10], c[11], bf), nvo_cvt16x2(c[12], c[13], bf),
+                           nvo_cvt16x2(c[14], c[15], bf));
+    }
+}
+
+constexpr uint32_t kX4Samples = 1024;  // samples of a 256-thread workgroup
+
+// dynamic LDS: (kX4Samples / S + 2) HeadRay
+__global__ void __launch_bounds__(256)
+k_ray_head_x4(nvo_ray_head_args a, NvoZeroPlan zero, uint32_t ray_blocks) {
+    if (blockIdx.x >= ray_blocks) {  // (uniform)
+        nvo_zero_plan_block(zero, blockIdx.x - ray_blocks);
+        return;
+    }
+    extern __shared__ __align__(16) unsigned char s_x4[];
+    HeadRay* const s_ray = reinterpret_cast<HeadRay*>(s_x4);
+    const uint32_t groups = a.R * a.S / 4u;  // (R * S < 2^32 / 12, S % 4 == 0)
+    const uint32_t g_first = blockIdx.x * 256u;
+    const uint32_t g_last = min(groups, g_first + 256u) - 1u;  // (g_first < groups: the grid covers exactly the groups)
+    const uint32_t r_first = 4u * g_first / a.S, n_rays = (4u * g_last + 3u) / a.S - r_first + 1u;  // <= 1024 / S + 2, <= 256
+    const uint32_t step = (uint32_t)a.step_dev[0];
+    // ---- the first lanes derive the workgroup's rays -- three hashes, ~30 dependent loads of intrinsics / pose /
+    // correction, ~200 flops each -- and write the outputs of those that START here while the other waves are busy
+    // with their bins
+    if (threadIdx.x < n_rays) {
+        const uint32_t r = r_first + threadIdx.x;
+        HeadRay h;
+        head_ray_derive(a, step, r, h);
+        s_ray[threadIdx.x] = h;
+        if (r * a.S >= 4u * g_first) {
+            HeadTargets t;
+            head_ray_gather(a, h, t);
+            head_ray_store(a, step, r, h, t);
+        }
+    }
+    // ---- first sampler level (k_lindisp_positions), the bins: edges j0 .. j0 + 4 once each.  They need the ray's jitter
+    // alone -- one hash, the same call the deriving lane makes -- so they are computed and stored in FRONT of the barrier,
+    // under the derive chain of the ray they belong to.
+    const uint32_t g = g_first + threadIdx.x;
+    const bool active = g < groups;
+    const uint32_t i0 = 4u * g, r = i0 / a.S, j0 = i0 - r * a.S;
+    float t[5];
+    if (active) {
+        const float jit0 = hash_uniform(a.seed, step, 3u, r);
+        const float s_near = spacing_fn(a.near_plane), s_far = spacing_fn(a.far_plane);
+        float b[5];
+#pragma unroll
+        for (uint32_t k = 0; k < 5; ++k) {
+            b[k] = lindisp_bin(j0 + k, a.S, &jit0, 0);
+            t[k] = spacing_fn_inv(b[k] * s_far + (1.f - b[k]) * s_near);
+        }
+        // (rows of S + 1 floats start 16-byte aligned on every fourth ray only: plain dword stores -- EXPERIMENTS.md 12.6)
+        float* __restrict__ sb = a.sbins + (size_t)r * (a.S + 1) + j0;
+        float* __restrict__ tb = a.tbins + (size_t)r * (a.S + 1) + j0;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            sb[k] = b[k];
+            tb[k] = t[k];
+        }
+        if (j0 + 4u == a.S) {
+            sb[4] = b[4];
+            tb[4] = t[4];
+        }
+    }
+    // workgroup barrier that orders LDS alone: __syncthreads() would also wait for every global store above to complete
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    if (!active) return;
+    // ---- ... and the positions of the four mid-points: three 16-byte stores, 48 bytes at a multiple of 48
+    const HeadRay hr = s_ray[r - r_first];
+    float p[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) nvo_contract_position01(hr.o, hr.d, (t[k] + t[k + 1]) * 0.5f, p + 3 * k);
+    float4* __restrict__ xp = reinterpret_cast<float4*>(a.x01) + 3 * (size_t)g;
+    xp[0] = make_float4(p[0], p[1], p[2], p[3]);
+    xp[1] = make_float4(p[4], p[5], p[6], p[7]);
+    xp[2] = make_float4(p[8], p[9], p[10], p[11]);
 }
 
 // Fused ray setup: ray generation + gather of the colour / depth / normal targets + the (d + 1) / 2
@@ -568,6 +712,13 @@ int nvo_sh_encode(nvo_stream_t stream, uint32_t R, uint32_t degree, const float*
     return nvo_sh_fwd_launch((hipStream_t)stream, R, degree, dirs01, out_half, 16, 16);
 }
 
+// NVO_RAY_HEAD_GENERIC=1 (tests and A/B; read per launch -- a captured graph keeps what it was captured with): the
+// thread-per-sample form for every shape
+static bool ray_head_generic() {
+    const char* const e = getenv("NVO_RAY_HEAD_GENERIC");
+    return e && e[0] == '1';
+}
+
 static int ray_head_launch(nvo_stream_t stream, const nvo_ray_head_args& a, uint32_t n_ranges, void* const* ptrs,
                            const uint64_t* bytes) {
     NvoZeroPlan zero;
@@ -577,10 +728,19 @@ static int ray_head_launch(nvo_stream_t stream, const nvo_ray_head_args& a, uint
         zero_blocks = nvo_zero_plan_build(n_ranges, ptrs, bytes, &zero);
         if (zero_blocks < 0) return NVO_ERR_INVALID;
     }
-    const uint32_t ray_blocks = (uint32_t)nvo_div_up((uint64_t)a.R * a.S, 256);
+    const uint64_t samples = (uint64_t)a.R * a.S;
+    const bool x4 = !ray_head_generic() && a.S % 4u == 0u && samples < (1ull << 32) / 12u && ((uintptr_t)a.x01 & 15u) == 0u &&
+                    ((uintptr_t)a.sh & 15u) == 0u;
+    const uint32_t ray_blocks = (uint32_t)nvo_div_up(samples, x4 ? kX4Samples : 256);
     if (ray_blocks + (uint32_t)zero_blocks == 0) return NVO_OK;
     NVO_PROF(stream, "ray_head[S%u]", a.S);
-    NVO_LAUNCH(k_ray_head, dim3(ray_blocks + (uint32_t)zero_blocks), dim3(256), 0, (hipStream_t)stream, a, zero, ray_blocks);
+    if (x4) {
+        const size_t lds = (kX4Samples / a.S + 2u) * sizeof(HeadRay);
+        NVO_LAUNCH(k_ray_head_x4, dim3(ray_blocks + (uint32_t)zero_blocks), dim3(256), lds, (hipStream_t)stream, a, zero,
+                   ray_blocks);
+    } else {
+        NVO_LAUNCH(k_ray_head, dim3(ray_blocks + (uint32_t)zero_blocks), dim3(256), 0, (hipStream_t)stream, a, zero, ray_blocks);
+    }
     NVO_CHECK_LAUNCH();
     return NVO_OK;
 }
