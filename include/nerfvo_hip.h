@@ -1064,6 +1064,92 @@ typedef struct nvo_knn_args {
 } nvo_knn_args;
 int nvo_knn_query(nvo_stream_t stream, const nvo_knn_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * L. Poisson surface reconstruction on a dense lattice (csrc/poisson.hip): oriented points in, the field chi out whose
+ *    iso-surface section J extracts -- the second half of the nerfstudio back-end's density mesh (the reference calls
+ *    Open3D's octree solver on the CPU; parity with it is UNPINNED).  DESIGN.md section 13 states the rule with every
+ *    sum's order; tests/helpers/poisson_oracle.py restates it in numpy.  fp32, fixed order, no float atomics: every entry
+ *    point equals the oracle bit for bit.
+ *    Lattice: nodes [nx][ny][nz], z fastest; 3 .. NVO_POISSON_MAX_NODES_PER_AXIS nodes per axis, fewer than 2^31 in all;
+ *    a field of C channels is planar [C][nx][ny][nz].  Coordinate of a point on an axis: g = (p - origin) / h,
+ *    c = clamp(floor(g), 0, cells - 1), t = g - float(c); weight of cell corner (dx, dy, dz): (ax * ay) * az with
+ *    a = d ? t : 1 - t.
+ *      nvo_poisson_splat       out[c][node] = sum of w * value over the points of the up to 8 cells that touch the node, cells
+ *                              ascending, points in sorted order, sequentially from 0.  value = 1 (values NULL, 1 channel),
+ *                              values[q][c], or values[q][c] / denom[q].
+ *      nvo_poisson_sample      out[q][c] = sum over the 8 corners (dx, dy, dz; dz fastest) of w * field[c][corner], from 0.
+ *      nvo_poisson_divergence  rhs = 0.5 * (((Vx[i+1]-Vx[i-1]) + (Vy[j+1]-Vy[j-1])) + (Vz[k+1]-Vz[k-1])) on interior nodes of
+ *                              field [3][nx][ny][nz], 0 on the boundary.
+ *      nvo_poisson_sweep       red-black Gauss-Seidel half-sweep of (sum of six neighbours - 6 chi) = rhs on the interior nodes
+ *                              with ((i + j + k) & 1) == color: s = ((((chi[i-1] + chi[i+1]) + chi[j-1]) + chi[j+1]) + chi[k-1])
+ *                              + chi[k+1]; chi = (s - rhs) * float(1/6).
+ *      nvo_poisson_restrict    coarse [nx/2+1 ..] = 4 * full weighting (1-2-1 per axis, / 64) of r = rhs - (s - 6 chi) around the
+ *                              even nodes: z lines, then y, then x, each (m + 2 c) + p; times 0.0625; 0 on the coarse boundary.
+ *      nvo_poisson_prolong     chi += trilinear interpolation of coarse on the interior nodes: (sum of the 1, 2, 4 or 8 coarse
+ *                              nodes, x outermost) * 0.5 per odd index.
+ *      nvo_poisson_residual_norm  *norm_bits = max(*norm_bits, bits of max |r| over the interior nodes) (integer atomic max
+ *                              of a non-negative float's bits; a NaN residual counts as +inf).  The caller zeroes the word.
+ *      nvo_poisson_vcycle      one V(2,2) cycle on chi over `levels` coarsenings (every axis: cells a multiple of 2^levels,
+ *                              at least 2 cells on the coarsest level): NVO_POISSON_SMOOTH_SWEEPS sweeps (red, then black),
+ *                              restrict, the coarse correction from 0, NVO_POISSON_COARSE_SWEEPS sweeps on the coarsest
+ *                              level, prolong, NVO_POISSON_SMOOTH_SWEEPS sweeps.  scratch: nvo_poisson_vcycle_scratch_bytes
+ *                              (0 = the lattice cannot be coarsened that often), 16-byte aligned.
+ *    No allocation, no dependency on the launch shape.
+ * ---------------------------------------------------------------------------------------------- */
+#define NVO_POISSON_MAX_NODES_PER_AXIS 4097
+#define NVO_POISSON_SMOOTH_SWEEPS 2
+#define NVO_POISSON_COARSE_SWEEPS 32
+typedef struct nvo_poisson_splat_args {
+    const float* points;         /* [K][3], sorted by cell (stable) */
+    const uint32_t* cell_start;  /* [(nx-1)(ny-1)(nz-1) + 1] first sorted row of each cell */
+    const float* values;         /* [K][channels] in the sorted order; NULL: 1 (channels = 1) */
+    const float* denom;          /* [K] optional: values are divided by it */
+    float* out;                  /* [channels][nx][ny][nz] */
+    uint32_t K;                  /* 1 .. 2^31 - 1 */
+    uint32_t channels;           /* 1 or 3 */
+    uint32_t nx, ny, nz;
+    float origin[3];
+    float h;                     /* > 0, finite */
+} nvo_poisson_splat_args;
+int nvo_poisson_splat(nvo_stream_t stream, const nvo_poisson_splat_args* args);
+
+typedef struct nvo_poisson_sample_args {
+    const float* field;          /* [channels][nx][ny][nz] */
+    const float* points;         /* [K][3], any order */
+    float* out;                  /* [K][channels] */
+    uint32_t K;
+    uint32_t channels;           /* 1 or 3 */
+    uint32_t nx, ny, nz;
+    float origin[3];
+    float h;
+} nvo_poisson_sample_args;
+int nvo_poisson_sample(nvo_stream_t stream, const nvo_poisson_sample_args* args);
+
+typedef struct nvo_poisson_level_args {
+    float* chi;                  /* [nx][ny][nz]: sweep, prolong (in/out); restrict, residual_norm (in) */
+    float* rhs;                  /* [nx][ny][nz]: divergence (out); sweep, restrict, residual_norm (in) */
+    const float* field;          /* divergence: [3][nx][ny][nz] */
+    float* coarse;               /* [(nx-1)/2+1][(ny-1)/2+1][(nz-1)/2+1]: restrict (out: coarse rhs), prolong (in: coarse chi) */
+    uint32_t* norm_bits;         /* residual_norm */
+    uint32_t nx, ny, nz;
+    uint32_t color;              /* sweep: 0 red, 1 black */
+} nvo_poisson_level_args;
+int nvo_poisson_divergence(nvo_stream_t stream, const nvo_poisson_level_args* args);
+int nvo_poisson_sweep(nvo_stream_t stream, const nvo_poisson_level_args* args);
+int nvo_poisson_restrict(nvo_stream_t stream, const nvo_poisson_level_args* args);
+int nvo_poisson_prolong(nvo_stream_t stream, const nvo_poisson_level_args* args);
+int nvo_poisson_residual_norm(nvo_stream_t stream, const nvo_poisson_level_args* args);
+
+typedef struct nvo_poisson_vcycle_args {
+    float* chi;                  /* [nx][ny][nz], boundary nodes 0 */
+    const float* rhs;            /* [nx][ny][nz] */
+    void* scratch;               /* nvo_poisson_vcycle_scratch_bytes(nx, ny, nz, levels) */
+    uint32_t nx, ny, nz;
+    uint32_t levels;             /* coarsenings, 0 .. 12 */
+} nvo_poisson_vcycle_args;
+uint64_t nvo_poisson_vcycle_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t levels);
+int nvo_poisson_vcycle(nvo_stream_t stream, const nvo_poisson_vcycle_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,32 @@ class LatticeArgs(C.Structure):
                 ("lower", _f * 3), ("step", _f * 3)]
 
 
+class PoissonSplatArgs(C.Structure):
+    """mirror of nvo_poisson_splat_args"""
+    _fields_ = [("points", _p), ("cell_start", _p), ("values", _p), ("denom", _p), ("out", _p), ("K", _u32), ("channels", _u32),
+                ("nx", _u32), ("ny", _u32), ("nz", _u32), ("origin", _f * 3), ("h", _f)]
+
+
+class PoissonSampleArgs(C.Structure):
+    """mirror of nvo_poisson_sample_args"""
+    _fields_ = [("field", _p), ("points", _p), ("out", _p), ("K", _u32), ("channels", _u32), ("nx", _u32), ("ny", _u32),
+                ("nz", _u32), ("origin", _f * 3), ("h", _f)]
+
+
+class PoissonLevelArgs(C.Structure):
+    """mirror of nvo_poisson_level_args"""
+    _fields_ = [("chi", _p), ("rhs", _p), ("field", _p), ("coarse", _p), ("norm_bits", _p), ("nx", _u32), ("ny", _u32),
+                ("nz", _u32), ("color", _u32)]
+
+
+class PoissonVcycleArgs(C.Structure):
+    """mirror of nvo_poisson_vcycle_args"""
+    _fields_ = [("chi", _p), ("rhs", _p), ("scratch", _p), ("nx", _u32), ("ny", _u32), ("nz", _u32), ("levels", _u32)]
+
+
+POISSON_MAX_NODES_PER_AXIS = 4097  # NVO_POISSON_MAX_NODES_PER_AXIS
+
+
 _SIGNATURES = {
     "nvo_last_error": (C.c_char_p, []),
     "nvo_version": (_int, []),
@@ -281,6 +307,16 @@ _SIGNATURES = {
     "nvo_lattice_positions": (_int, [_p, C.POINTER(LatticeArgs)]),
     # group K
     "nvo_knn_query": (_int, [_p, C.POINTER(KnnArgs)]),
+    # group L
+    "nvo_poisson_splat": (_int, [_p, C.POINTER(PoissonSplatArgs)]),
+    "nvo_poisson_sample": (_int, [_p, C.POINTER(PoissonSampleArgs)]),
+    "nvo_poisson_divergence": (_int, [_p, C.POINTER(PoissonLevelArgs)]),
+    "nvo_poisson_sweep": (_int, [_p, C.POINTER(PoissonLevelArgs)]),
+    "nvo_poisson_restrict": (_int, [_p, C.POINTER(PoissonLevelArgs)]),
+    "nvo_poisson_prolong": (_int, [_p, C.POINTER(PoissonLevelArgs)]),
+    "nvo_poisson_residual_norm": (_int, [_p, C.POINTER(PoissonLevelArgs)]),
+    "nvo_poisson_vcycle_scratch_bytes": (_u64, [_u32, _u32, _u32, _u32]),
+    "nvo_poisson_vcycle": (_int, [_p, C.POINTER(PoissonVcycleArgs)]),
     # group E
     "nvo_adam_step": (_int, [_p, C.POINTER(AdamArgs), _u32, C.POINTER(AdamGroup), C.POINTER(AdamTail)]),
     "nvo_opt_commit": (_int, [_p, C.POINTER(OptCommitArgs), C.POINTER(StepScalars)]),

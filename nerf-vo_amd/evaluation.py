@@ -23,7 +23,9 @@ reference uses Open3D and scipy on the CPU; here pointcloud.py does the cloud op
 is a HIP kernel (csrc/nn.hip).  For the nerfstudio back-end, whose density mesh in the reference is a point cloud
 followed by Open3D's Poisson reconstruction, ``EvaluationRenderer.render_point_cloud`` produces the cloud
 (``pointcloud/pointcloud_from_nerf.ply``; mapping/renderer.py, the k-NN kernel csrc/knn.hip under its outlier removal) and
-``calculate_metrics_3d_cloud`` / ``Evaluator3D.calculate_metrics_3d_clouds`` score it as a cloud; the reconstruction is not built.
+``calculate_metrics_3d_cloud`` / ``Evaluator3D.calculate_metrics_3d_clouds`` score it as a cloud; ``render_mesh(source='nerf')``
+reconstructs the mesh from the same cloud (poisson.py: the project's dense-lattice Poisson rule, csrc/poisson.hip; parity with
+Open3D's octree solver unpinned).
 
 The numeric functions are pinned by the reference's own outputs: tests/golden/make_golden_evaluation.py and
 make_golden_metrics3d.py execute the reference's definitions on seeded inputs and tests/test_evaluation_cpu.py /
@@ -223,14 +225,16 @@ class EvaluationRenderer:
                                f"{self.dir_prediction}/{folder}/depth/{index:06d}.png")
         return indices
 
-    def render_mesh(self, source: str = "frames", mode: str = "evaluation_frames") -> str:
+    def render_mesh(self, source: str = "frames", mode: str = "evaluation_frames", **kwargs) -> str:
         """``source='frames'``: ``mesh/mesh_from_<mode>.ply`` fused from the colour / depth files ``render_frames(mode)``
         wrote (rendered first when their folder is absent) at the ground-truth poses of those frames (renderer.py:126-164,
         265-273): TSDF fusion on the GPU, nerf_vo_amd/tsdf.py.  ``source='nerf'``: ``mesh/mesh_from_nerf.ply``, the
-        density iso-surface of the model cropped to the ground-truth mesh's box (``_render_mesh_from_nerf``).  Returns the
-        file's path."""
+        mesh of the model's field cropped to the ground-truth mesh's box (``_render_mesh_from_nerf``; ``kwargs`` go to the
+        model renderer's ``render_mesh``).  Returns the file's path."""
         if source == "nerf":
-            return self._render_mesh_from_nerf()
+            return self._render_mesh_from_nerf(**kwargs)
+        if kwargs:
+            raise TypeError(f"render_mesh(source={source!r}) takes no further arguments, got {sorted(kwargs)}")
         if source != "frames":
             raise NotImplementedError(source)
         from .tsdf import integrate_mesh
@@ -263,37 +267,38 @@ class EvaluationRenderer:
         lower, upper = np.min(corners_pred, axis=1)[:3], np.max(corners_pred, axis=1)[:3]
         return lower_gt, upper_gt, matrix, lower, upper
 
-    def _render_mesh_from_nerf(self) -> str:
+    def _render_mesh_from_nerf(self, **kwargs) -> str:
         """The reference's ``_render_mesh_from_nerf`` (renderer.py:166-210): the box of the ground-truth mesh's vertices is
-        mapped into the model's frame by inv(matrix_pred2gt_scaled), the model's renderer extracts its density iso-surface
-        over the box of the mapped corners at 1/64 m (``mesh/mesh_from_nerf_raw.ply``), and that mesh, mapped back by
-        matrix_pred2gt_scaled and cropped to the ground-truth box, is ``mesh/mesh_from_nerf.ply``.  Open3D's transform and
-        crop are meshing.transform_mesh / crop_mesh here (parity with Open3D unpinned)."""
+        mapped into the model's frame by inv(matrix_pred2gt_scaled), the model's renderer writes its mesh over the box of
+        the mapped corners (``mesh/mesh_from_nerf_raw.ply``: the density iso-surface at 1/64 m for the occupancy-grid
+        back-end, the Poisson reconstruction of the oriented cloud for the nerfstudio back-end, which takes ``kwargs``), and
+        that mesh, mapped back by matrix_pred2gt_scaled and cropped to the ground-truth box, is ``mesh/mesh_from_nerf.ply``;
+        vertex colours of the raw file, when it has them, are kept.  Open3D's transform and crop are
+        meshing.transform_mesh / crop_mesh here (parity with Open3D unpinned)."""
         from .meshing import crop_mesh, read_mesh, transform_mesh, write_mesh
 
         if not callable(getattr(self.nerf, "render_mesh", None)):
             raise NotImplementedError(
                 f"render_mesh(source='nerf'): {type(self.nerf).__name__} has no render_mesh(file_mesh, resolution, lower_bound, "
                 "upper_bound).  The occupancy-grid back-end has one (InstantNGPRenderer.render_mesh -> "
-                "pyngp.Testbed.compute_and_save_marching_cubes_mesh).  The reference's nerfstudio one is a point cloud followed by "
-                "Open3D's Poisson reconstruction: the point cloud is built (render_point_cloud -> pointcloud/"
-                "pointcloud_from_nerf.ply, scored by Evaluator3D.calculate_metrics_3d_clouds), the Poisson reconstruction is not")
+                "pyngp.Testbed.compute_and_save_marching_cubes_mesh), and so has the nerfstudio back-end "
+                "(NerfstudioRenderer.render_mesh: the oriented point cloud and its Poisson reconstruction, poisson.py)")
         voxel_size = 1 / 64
         os.makedirs(f"{self.dir_prediction}/mesh", exist_ok=True)
         lower_gt, upper_gt, matrix, lower, upper = self._ground_truth_box_in_model_frame()
         resolution = ((upper - lower) * self.pred2gt_transformation["scale_pred2gt"] / voxel_size).astype(int)
         file_raw = f"{self.dir_prediction}/mesh/mesh_from_nerf_raw.ply"
-        self.nerf.render_mesh(file_mesh=file_raw, resolution=resolution, lower_bound=lower, upper_bound=upper)
-        vertices, faces = read_mesh(file_raw)[:2]
-        vertices, faces, _ = crop_mesh(transform_mesh(vertices, matrix), faces, lower_gt, upper_gt)
+        self.nerf.render_mesh(file_mesh=file_raw, resolution=resolution, lower_bound=lower, upper_bound=upper, **kwargs)
+        vertices, faces, colors = read_mesh(file_raw)[:3]
+        vertices, faces, keep = crop_mesh(transform_mesh(vertices, matrix), faces, lower_gt, upper_gt)
         if vertices.shape[0] == 0 or faces.shape[0] == 0:
             raise RuntimeError(
                 f"render_mesh(source='nerf'): nothing of {file_raw} lies inside the ground-truth mesh's box "
                 f"{lower_gt.tolist()} .. {upper_gt.tolist()}, so mesh_from_nerf.ply is not written: the density never crosses the "
                 "iso-surface threshold there (thresh of compute_and_save_marching_cubes_mesh, 2.5 by default) -- train longer or "
-                "extract at a lower thresh")
+                "extract at a lower thresh (a Poisson mesh: every vertex was trimmed, or the cloud is empty there)")
         file_mesh = f"{self.dir_prediction}/mesh/mesh_from_nerf.ply"
-        write_mesh(file_mesh, vertices, faces)
+        write_mesh(file_mesh, vertices, faces, colors=None if colors is None else colors[keep])
         return file_mesh
 
     def render_point_cloud(self, num_points: int = 33554432, **kwargs) -> str:

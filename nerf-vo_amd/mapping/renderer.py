@@ -104,22 +104,15 @@ class NerfstudioRenderer(NeRFRenderer):
         depth = (outputs["depth"] / bundle.metadata["directions_norm"]).cpu().numpy()[..., 0]  # z-depth
         return color, depth
 
-    def render_point_cloud(self, file_point_cloud: str, lower_bound, upper_bound, num_points: int = 33554432,
-                           remove_outliers: bool = True, std_ratio: float = 10.0, min_accumulation: float | None = 0.5,
-                           seed: int = 0) -> dict:
-        """The first half of the reference's ``NerfstudioRenderer.render_mesh`` (evaluation/nerf_renderer.py:170-209
-        there, ``predict_normals=True``): nerfstudio's ``generate_point_cloud`` -- an oriented, coloured cloud of
-        ``num_points`` points back-projected from random training rays inside the box, cleaned by
-        ``remove_statistical_outlier(nb_neighbors=20, std_ratio)`` (pointcloud.py: the k-NN kernel), normals turned
-        towards the cameras -- written to ``file_point_cloud`` as a binary .ply with ``x y z nx ny nz red green blue``
-        and no faces.  The second half, Open3D's Poisson reconstruction of that cloud, is not built.  Returns the cloud
-        (``points``, ``normals``, ``colors``, ``view_directions`` CPU tensors, rows as in the file) and the counts
-        ``generated`` (before the outlier removal) / ``kept``."""
-        from ..meshing import write_mesh
+    def _oriented_cloud(self, what: str, lower_bound, upper_bound, num_points: int, remove_outliers: bool, std_ratio: float,
+                        min_accumulation, seed: int) -> dict:
+        """The cloud of ``render_point_cloud`` and ``render_mesh`` as GPU tensors: ``generate_point_cloud``, the statistical
+        outlier removal, normals turned towards the cameras; ``generated`` / ``kept`` are the counts before / after the
+        removal."""
         from ..pointcloud import remove_statistical_outlier
 
         if not getattr(self.pipeline.model.config, "predict_normals", False):
-            raise RuntimeError("render_point_cloud: the model was set up with predict_normals=False and has no normals to "
+            raise RuntimeError(f"{what}: the model was set up with predict_normals=False and has no normals to "
                                "orient the cloud with -- train with predict_normals=True (the reference's configuration)")
         cloud = generate_point_cloud(self.pipeline, self.matrices_origin2frame_training, lower_bound, upper_bound,
                                      num_points=num_points, min_accumulation=min_accumulation, seed=seed)
@@ -129,11 +122,56 @@ class NerfstudioRenderer(NeRFRenderer):
             points, index = remove_statistical_outlier(points, nb_neighbors=20, std_ratio=std_ratio)
             normals, colors, views = normals[index], colors[index], views[index]
         normals = orient_normals_towards_cameras(normals, views)
-        out = {"points": points.cpu(), "normals": normals.cpu(), "colors": colors.cpu(), "view_directions": views.cpu(),
-               "generated": generated, "kept": int(points.shape[0])}
+        return {"points": points, "normals": normals, "colors": colors, "view_directions": views, "generated": generated,
+                "kept": int(points.shape[0])}
+
+    def render_point_cloud(self, file_point_cloud: str, lower_bound, upper_bound, num_points: int = 33554432,
+                           remove_outliers: bool = True, std_ratio: float = 10.0, min_accumulation: float | None = 0.5,
+                           seed: int = 0) -> dict:
+        """The first half of the reference's ``NerfstudioRenderer.render_mesh`` (evaluation/nerf_renderer.py:170-209
+        there, ``predict_normals=True``): nerfstudio's ``generate_point_cloud`` -- an oriented, coloured cloud of
+        ``num_points`` points back-projected from random training rays inside the box, cleaned by
+        ``remove_statistical_outlier(nb_neighbors=20, std_ratio)`` (pointcloud.py: the k-NN kernel), normals turned
+        towards the cameras -- written to ``file_point_cloud`` as a binary .ply with ``x y z nx ny nz red green blue``
+        and no faces.  The second half, the Poisson reconstruction of that cloud, is ``render_mesh``.  Returns the cloud
+        (``points``, ``normals``, ``colors``, ``view_directions`` CPU tensors, rows as in the file) and the counts
+        ``generated`` (before the outlier removal) / ``kept``."""
+        from ..meshing import write_mesh
+
+        cloud = self._oriented_cloud("render_point_cloud", lower_bound, upper_bound, num_points, remove_outliers, std_ratio,
+                                     min_accumulation, seed)
+        out = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in cloud.items()}
         write_mesh(file_point_cloud, out["points"], torch.zeros(0, 3, dtype=torch.int64), colors=out["colors"],
                    normals=out["normals"])
         return out
+
+    def render_mesh(self, file_mesh: str, resolution, lower_bound, upper_bound, num_points: int = 33554432, depth: int = 9,
+                    remove_outliers: bool = True, std_ratio: float = 10.0, min_accumulation: float | None = 0.5, seed: int = 0,
+                    **poisson_kwargs) -> dict:
+        """The reference's ``NerfstudioRenderer.render_mesh`` with ``predict_normals=True`` (evaluation/nerf_renderer.py:184-207
+        there): the oriented, coloured cloud of ``render_point_cloud`` (same arguments, same rule; no file in between),
+        its Poisson reconstruction over ``lower_bound..upper_bound`` at ``depth`` (poisson.poisson_reconstruct: the
+        project's dense-lattice rule, DESIGN.md section 13 -- parity with Open3D's octree solver is unpinned), the vertices
+        of low density dropped, written to ``file_mesh`` with ``x y z red green blue`` and the faces.  ``resolution`` is
+        accepted and ignored, as the reference's Poisson branch ignores it.  ``poisson_kwargs`` (``scale``, ``cycles``,
+        ``trim_quantile``, ``min_density``) go to ``poisson_reconstruct``.  Returns its ``info`` with the cloud's counts
+        ``generated`` / ``kept`` added."""
+        from ..meshing import write_mesh
+        from ..poisson import poisson_reconstruct
+
+        cloud = self._oriented_cloud("render_mesh", lower_bound, upper_bound, num_points, remove_outliers, std_ratio,
+                                     min_accumulation, seed)
+        if remove_outliers and 2 * cloud["kept"] < cloud["generated"]:
+            import warnings
+
+            warnings.warn(f"render_mesh: the outlier removal kept {cloud['kept']} of {cloud['generated']} points.  Rays are drawn "
+                          "with replacement: with more points than training pixels a pixel is drawn many times, 20 identical "
+                          "points have a mean neighbour distance of 0, and the rule drops points at 0 -- ask for fewer points")
+        vertices, faces, colors, info = poisson_reconstruct(cloud["points"], cloud["normals"], cloud["colors"], lower=lower_bound,
+                                                            upper=upper_bound, depth=depth, **poisson_kwargs)
+        write_mesh(file_mesh, vertices, faces, colors=colors)
+        info.update(generated=cloud["generated"], kept=cloud["kept"])
+        return info
 
 
 # generate_point_cloud gives up after this many consecutive batches without a single kept point

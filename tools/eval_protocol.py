@@ -103,15 +103,34 @@ def _log(mapper):
               f"half_finite {bool(torch.isfinite(eng.working_copy_float()).all())} losses {eng.loss_dict()}", file=sys.stderr, flush=True)
 
 
+def _mesh_nerf_defaults(points, depth, training_pixels):
+    """Points and depth of the nerfstudio density mesh where the command line leaves them open.  The reference asks for
+    33 554 432 points at depth 9 from some 1e8 training pixels.  The protocol's frames are small: rays are drawn with
+    replacement, a pixel drawn 20 times is 20 identical points, whose mean neighbour distance is 0, and the outlier rule
+    drops points at 0 -- so at most a quarter of the training pixels; and a lattice whose surface cells hold fewer than
+    about four points has densities below the trim's floor -- so at most floor(log4(points / 24)), a cube's 6 * 4^depth
+    surface cells.  Both constants, the quarter and the four points per cell, are reasoned, not tuned: each was tried in
+    one run of this tool (EXPERIMENTS.md section 19) and nothing else was measured."""
+    import math
+
+    if points is None:
+        points = min(33554432, max(int(training_pixels) // 4, 1))
+    if depth is None:
+        depth = max(2, min(9, int(math.floor(math.log(max(points / 24.0, 16.0), 4.0)))))
+    return int(points), int(depth)
+
+
 def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, eval_frames=8, chunk=8, device="cuda:0",
         camera_optimizer_mode=None, pose_noise=None, deterministic=False, seed=42, dynamic_loss_scale=None, out_dir=None,
         quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None, mesh=False, metrics_3d=False,
-        mesh_nerf=False, pointcloud=False, pointcloud_points=33554432):
+        mesh_nerf=False, pointcloud=False, pointcloud_points=33554432, poisson_depth=None, mesh_nerf_points=None):
     """``method``: 'nerfstudio' (the default mapper) or 'instant-ngp' (the occupancy-grid back-end through the pyngp facade,
     /root/reference/nerf_vo/mapping/instant_ngp.py + evaluation/nerf_renderer.py:221-320; the room is shrunk by
     ``scene_scale``, default 0.5, so that it lies inside that back-end's scene box: it takes poses as they come).
-    ``mesh_nerf`` (instant-ngp only): also ``render_mesh(source='nerf')``, the density iso-surface cropped to the ground-truth
-    mesh's box (run.py:72); with ``metrics_3d`` the table gains its row.
+    ``mesh_nerf``: also ``render_mesh(source='nerf')`` cropped to the ground-truth mesh's box (run.py:72) -- the density
+    iso-surface of the occupancy-grid back-end, the Poisson reconstruction (at ``poisson_depth``) of a cloud of
+    ``mesh_nerf_points`` points for the nerfstudio back-end; with ``metrics_3d`` the table gains its row.  Their defaults
+    are the reference's 33 554 432 points and depth 9 brought down to the protocol's small frames (``_mesh_nerf_defaults``).
     ``pointcloud`` (nerfstudio only): also ``render_point_cloud(num_points=pointcloud_points)`` -- the oriented, coloured cloud
     of the field, outliers removed, cropped to the ground-truth mesh's box -- and its score, results/metrics_3d_pointcloud.csv."""
     entry.build()
@@ -127,8 +146,6 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
     out_dir = out_dir or tempfile.mkdtemp(prefix="nvo_eval_")
     n_frames = keyframes * frame_stride  # dataset frames; every frame_stride-th one is a keyframe (configs: frame_stride 2)
     ngp = method == "instant-ngp"
-    if mesh_nerf and not ngp:
-        raise SystemExit("--mesh-nerf needs --method instant-ngp (the nerfstudio back-end has no density mesh)")
     if pointcloud and ngp:
         raise SystemExit("--pointcloud needs --method nerfstudio (the occupancy-grid back-end predicts no normals)")
     if ngp and abs(width / height - 1200.0 / 680.0) > 0.01:
@@ -196,9 +213,15 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
     mesh_nerf_info = None
     if mesh_nerf:  # run.py:72: mesh/mesh_from_nerf_raw.ply and its crop mesh/mesh_from_nerf.ply
         t_mesh = time.perf_counter()
-        file_mesh = renderer.render_mesh(source="nerf")
+        if ngp:
+            file_mesh = renderer.render_mesh(source="nerf")
+        else:
+            mesh_nerf_points, poisson_depth = _mesh_nerf_defaults(mesh_nerf_points, poisson_depth, keyframes * height * width)
+            file_mesh = renderer.render_mesh(source="nerf", num_points=mesh_nerf_points, depth=poisson_depth)
         mesh_nerf_info = {"file": file_mesh if not own_dir else os.path.basename(file_mesh), "bytes": os.path.getsize(file_mesh),
                           "seconds": time.perf_counter() - t_mesh}
+        if not ngp:
+            mesh_nerf_info.update(points_requested=mesh_nerf_points, poisson_depth=poisson_depth)
     cloud_info = None
     if pointcloud:  # the first half of the reference's nerfstudio render_mesh: pointcloud/pointcloud_from_nerf.ply, and its score
         import pandas as pd
@@ -294,8 +317,13 @@ if __name__ == "__main__":
     ap.add_argument("--mesh", action="store_true", help="also fuse the rendered evaluation frames into mesh/mesh_from_evaluation_frames.ply")
     ap.add_argument("--metrics-3d", action="store_true", help="also score the mesh against the fused ground-truth mesh "
                     "(results/metrics_3d.csv); implies --mesh")
-    ap.add_argument("--mesh-nerf", action="store_true", help="instant-ngp only: also extract the density iso-surface, cropped to "
-                    "the ground-truth mesh's box (mesh/mesh_from_nerf.ply); with --metrics-3d the table gains its row")
+    ap.add_argument("--mesh-nerf", action="store_true", help="also the mesh of the field itself, cropped to the ground-truth mesh's "
+                    "box (mesh/mesh_from_nerf.ply): the density iso-surface (instant-ngp) or the Poisson reconstruction of the "
+                    "oriented point cloud (nerfstudio); with --metrics-3d the table gains its row")
+    ap.add_argument("--poisson-depth", type=int, default=None, help="nerfstudio --mesh-nerf: depth of the Poisson lattice (2..10); "
+                    "default: the reference's 9, lowered until a surface cell holds about four points")
+    ap.add_argument("--mesh-nerf-points", type=int, default=None, help="nerfstudio --mesh-nerf: points of the cloud before "
+                    "outlier removal; default: the reference's 33554432, at most a quarter of the training pixels")
     ap.add_argument("--pointcloud", action="store_true", help="nerfstudio only: also export the field's oriented point cloud, "
                     "cropped to the ground-truth mesh's box (pointcloud/pointcloud_from_nerf.ply), and score it "
                     "(results/metrics_3d_pointcloud.csv)")
@@ -305,4 +333,5 @@ if __name__ == "__main__":
         pose_noise=a.pose_noise, deterministic=a.deterministic, seed=a.seed, quiet=False,
         dynamic_loss_scale=False if a.static_loss_scale else None, keyframe_views=not a.no_keyframe_views,
         method=a.method, scene_scale=a.scene_scale, mesh=a.mesh, metrics_3d=a.metrics_3d, mesh_nerf=a.mesh_nerf,
-        pointcloud=a.pointcloud, pointcloud_points=a.pointcloud_points)
+        pointcloud=a.pointcloud, pointcloud_points=a.pointcloud_points, poisson_depth=a.poisson_depth,
+        mesh_nerf_points=a.mesh_nerf_points)
