@@ -327,15 +327,3 @@ int nvo_reduce_by_camera(hipStream_t stream, uint32_t R, uint32_t K, const float
 // colour head: tile_partial [R * tiles_per_ray][48] -> per_ray [R][48] (tiles ascending); d_sh[r] = per_ray[r][32..48)
 int nvo_color_tiles_to_rays(hipStream_t stream, uint32_t R, uint32_t tiles_per_ray, const float* tile_partial,
                             float* per_ray, float* d_sh);
-
-// ---- render_legacy.hip ---------------------------------------------------------------------------
-// The per-ray kernels in their previous form (NVO_RAY_LEGACY=1: tests and A/B only).  The launchers of render.hip have
-// checked the arguments and call hipGetLastError afterwards.
-struct nvo_weights_pdf_args;
-struct nvo_main_loss_args;
-struct nvo_prop_loss_args;
-#define NVO_HIDDEN __attribute__((visibility("hidden")))
-NVO_HIDDEN void nvo_ray_legacy_weights_pdf(hipStream_t stream, const nvo_weights_pdf_args& a);
-NVO_HIDDEN void nvo_ray_legacy_main_render_loss(hipStream_t stream, const nvo_main_loss_args& a);
-NVO_HIDDEN void nvo_ray_legacy_prop_loss(hipStream_t stream, const nvo_prop_loss_args& a0, const nvo_prop_loss_args& a1,
-                                         uint32_t blocks0, uint32_t blocks1);

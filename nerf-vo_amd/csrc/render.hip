@@ -17,7 +17,6 @@
 #include "../../include/nerfvo_hip.h"
 
 #include <float.h>
-#include <stdlib.h>
 
 namespace {
 
@@ -702,13 +701,6 @@ k_prop_loss(nvo_prop_loss_args a0, nvo_prop_loss_args a1, uint32_t blocks0) {
 // ---------------------------------------------------------------------------------------------
 // exported entry points (group C of include/nerfvo_hip.h)
 // ---------------------------------------------------------------------------------------------
-// NVO_RAY_LEGACY=1 (tests and A/B; read per launch -- a captured graph keeps what it was captured with): the kernels
-// of render_legacy.hip instead
-static bool ray_legacy() {
-    const char* const e = getenv("NVO_RAY_LEGACY");
-    return e && e[0] == '1';
-}
-
 extern "C" {
 
 int nvo_weights_pdf(nvo_stream_t stream, const nvo_weights_pdf_args* args) {
@@ -721,8 +713,7 @@ int nvo_weights_pdf(nvo_stream_t stream, const nvo_weights_pdf_args* args) {
     NVO_REQUIRE(!a.x01_out || (a.origins && a.directions && a.S_out > 0), "weights_pdf: x01_out needs origins, directions and S_out");
     if (a.R == 0) return NVO_OK;
     NVO_PROF(stream, "weights_pdf[S%u]", a.S);
-    if (ray_legacy()) nvo_ray_legacy_weights_pdf((hipStream_t)stream, a);
-    else NVO_LAUNCH(k_weights_pdf, dim3(nvo_div_up(a.R, kRaysPerBlock)), dim3(kRayBlock), 0, (hipStream_t)stream, a);
+    NVO_LAUNCH(k_weights_pdf, dim3(nvo_div_up(a.R, kRaysPerBlock)), dim3(kRayBlock), 0, (hipStream_t)stream, a);
     NVO_CHECK_LAUNCH();
     return NVO_OK;
 }
@@ -738,8 +729,7 @@ int nvo_main_render_loss(nvo_stream_t stream, const nvo_main_loss_args* args) {
     NVO_REQUIRE(!a.tile_live || (a.dpre && (a.S & 15u) == 0u), "main_render_loss: tile_live needs training mode and S %% 16 == 0 (S = %u)", a.S);
     if (a.R == 0) return NVO_OK;
     NVO_PROF(stream, "main_render_loss");
-    if (ray_legacy()) nvo_ray_legacy_main_render_loss((hipStream_t)stream, a);
-    else NVO_LAUNCH(k_main_render_loss, dim3(nvo_div_up(a.R, kRaysPerBlock)), dim3(kRayBlock), 0, (hipStream_t)stream, a);
+    NVO_LAUNCH(k_main_render_loss, dim3(nvo_div_up(a.R, kRaysPerBlock)), dim3(kRayBlock), 0, (hipStream_t)stream, a);
     NVO_CHECK_LAUNCH();
     return NVO_OK;
 }
@@ -754,8 +744,7 @@ int nvo_prop_loss(nvo_stream_t stream, const nvo_prop_loss_args* args) {
     if (a.R == 0) return NVO_OK;
     NVO_PROF(stream, "prop_loss[S%u]", a.S);
     const uint32_t blocks = nvo_div_up(a.R, kRaysPerBlock);
-    if (ray_legacy()) nvo_ray_legacy_prop_loss((hipStream_t)stream, a, a, blocks, 0);
-    else NVO_LAUNCH(k_prop_loss, dim3(blocks), dim3(kRayBlock), 0, (hipStream_t)stream, a, a, blocks);
+    NVO_LAUNCH(k_prop_loss, dim3(blocks), dim3(kRayBlock), 0, (hipStream_t)stream, a, a, blocks);
     NVO_CHECK_LAUNCH();
     return NVO_OK;
 }
@@ -772,8 +761,7 @@ int nvo_prop_loss_pair(nvo_stream_t stream, const nvo_prop_loss_args* args0, con
     const uint32_t b0 = nvo_div_up(args0->R, kRaysPerBlock), b1 = nvo_div_up(args1->R, kRaysPerBlock);
     if (b0 + b1 == 0) return NVO_OK;
     NVO_PROF(stream, "prop_loss[S%u+S%u]", args0->S, args1->S);
-    if (ray_legacy()) nvo_ray_legacy_prop_loss((hipStream_t)stream, *args0, *args1, b0, b1);
-    else NVO_LAUNCH(k_prop_loss, dim3(b0 + b1), dim3(kRayBlock), 0, (hipStream_t)stream, *args0, *args1, b0);
+    NVO_LAUNCH(k_prop_loss, dim3(b0 + b1), dim3(kRayBlock), 0, (hipStream_t)stream, *args0, *args1, b0);
     NVO_CHECK_LAUNCH();
     return NVO_OK;
 }
