@@ -734,6 +734,40 @@ int nvo_ngp_thickness_splat(nvo_stream_t stream, uint32_t n, const void* density
                             const uint32_t* cell_idx, float* fresh);
 int nvo_fill_i32(nvo_stream_t stream, uint32_t n, int32_t* ptr, int32_t value);
 
+/* Rendered surface normals of the occupancy-grid back-end (inference only): the field's analytic normal is the negated
+ * gradient of its density, the rule the nerfacto path renders (`outputs['normals']`).  The chain is the library's own:
+ * nvo_fwd with the module option prepare_input_gradients on -> nvo_ngp_normal_seed -> nvo_bwd with dL_dparams = NULL,
+ * whose dL_dinput is d(seed * pre-activation) / d(x01) of every packed sample (the exponential activation multiplies the
+ * gradient by a positive number: the pre-activation's gradient has the density's direction) -> nvo_ngp_composite_normals.
+ *  ngp_normal_seed       : rows 0 .. n-1 of d_density_out (fp16 [..][16], what nvo_bwd reads as dL_doutput): column 0 =
+ *                          seed, columns 1..15 = 0
+ *  ngp_composite_normals : one wave per ray over its packed range, the chunked walk of nvo_ngp_composite_loss's inference
+ *                          pass.  w_i = (1 - exp(-dd_i)) T_i, dd_i = min(exp(pre_i) dt_i, 128), T_i from the inclusive wave
+ *                          scan plus carry_in: the same operations in the same order, so the weights are the colour pass's
+ *                          bit for bit.  g_k = dx01[off + i][k] * aabb_inv_size, zeroed on an axis where the sample's
+ *                          unclamped coordinate (o + t d - aabb_lo) * aabb_inv_size is not strictly inside (0, 1) (the
+ *                          mask of nvo_ngp_positions_bwd); n_i = -g / (|g| + 1e-10); out_normal[r] (=|+=) sum_i w_i n_i,
+ *                          UNNORMALISED.  Rays without samples write (or add) zeros; a ray whose range does not lie inside
+ *                          the packed capacity is treated as empty.  No float atomics: wave sums in a fixed order. */
+typedef struct nvo_ngp_normal_args {
+    uint32_t R, capacity;
+    const uint32_t* counts;      /* [R] */
+    const uint32_t* offsets;     /* [R+1] */
+    const float* t;              /* [capacity] */
+    const float* dt;             /* [capacity] */
+    const void* density_out;     /* fp16 [capacity][density_stride], pre-activation in column 0 */
+    uint32_t density_stride;
+    const float* dx01;           /* [capacity][3]: nvo_bwd's dL_dinput for the seeded rows */
+    const float* origins;        /* [R][3] */
+    const float* directions;     /* [R][3] */
+    float aabb_lo, aabb_hi;
+    const float* carry_in;       /* [R] nullable: optical depth gathered in earlier rounds */
+    uint32_t accumulate;         /* 0: out_normal is overwritten; else added to (a later round) */
+    float* out_normal;           /* [R][3] */
+} nvo_ngp_normal_args;
+int nvo_ngp_normal_seed(nvo_stream_t stream, uint32_t n, float seed, void* d_density_out);
+int nvo_ngp_composite_normals(nvo_stream_t stream, const nvo_ngp_normal_args* args);
+
 /* ------------------------------------------------------------------------------------------------
  * E. Optimiser: torch.optim.Adam (no AMSGrad, L2 weight decay folded into the gradient) under torch's GradScaler --
  *    a parameter group whose gradients hold a non-finite value is skipped, its step counter does not advance, and

@@ -144,6 +144,13 @@ class NgpAliveArgs(C.Structure):
                 ("kept_base", _u32), ("t_next", _p), ("resume_out", _p), ("carry_out", _p)]
 
 
+class NgpNormalArgs(C.Structure):
+    """mirror of nvo_ngp_normal_args"""
+    _fields_ = [("R", _u32), ("capacity", _u32), ("counts", _p), ("offsets", _p), ("t", _p), ("dt", _p), ("density_out", _p),
+                ("density_stride", _u32), ("dx01", _p), ("origins", _p), ("directions", _p), ("aabb_lo", _f), ("aabb_hi", _f),
+                ("carry_in", _p), ("accumulate", _u32), ("out_normal", _p)]
+
+
 class TsdfArgs(C.Structure):
     """mirror of nvo_tsdf_args"""
     _fields_ = [("tsdf", _p), ("weight", _p), ("color", _p), ("frames", _p), ("depth", _p), ("rgb", _p),
@@ -295,6 +302,8 @@ _SIGNATURES = {
     "nvo_ngp_thickness": (_int, [_p, _u32, _p, _u32, _int, _p]),
     "nvo_ngp_thickness_splat": (_int, [_p, _u32, _p, _u32, _p, _p]),
     "nvo_fill_i32": (_int, [_p, _u32, _p, _i32]),
+    "nvo_ngp_normal_seed": (_int, [_p, _u32, _f, _p]),
+    "nvo_ngp_composite_normals": (_int, [_p, C.POINTER(NgpNormalArgs)]),
     # group H
     "nvo_tsdf_integrate": (_int, [_p, C.POINTER(TsdfArgs)]),
     # group I

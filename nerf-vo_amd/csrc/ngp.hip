@@ -459,6 +459,64 @@ k_fill_i32(uint32_t n, int32_t* __restrict__ p, int32_t v) {
     if (i < n) p[i] = v;
 }
 
+// dL/d(density_out) rows of the normals chain: column 0 = seed, columns 1..15 = 0 (one 32-byte row per thread, two
+// 16-byte stores)
+__global__ void __launch_bounds__(256)
+k_ngp_normal_seed(uint32_t n, uint32_t seed_bits, uint4* __restrict__ rows) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    rows[2 * (size_t)i] = make_uint4(seed_bits, 0u, 0u, 0u);
+    rows[2 * (size_t)i + 1] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// Rendered normals: sum_i w_i n_i per ray, the weights of the colour pass (k_ngp_composite_loss, inference: pass 1) --
+// the same loads, exponentials, scan and carry in the same order -- times the unit negated density gradient of every
+// sample.  One wave per ray, chunks of 64; wave sums in a fixed order, no atomics.
+__global__ void __launch_bounds__(256)
+k_ngp_composite_normals(nvo_ngp_normal_args a, float aabb_inv_size) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= a.R) return;
+    uint32_t n = a.counts[r];
+    const uint32_t base = a.offsets[r];
+    if (base >= a.capacity || n > a.capacity - base) n = 0u;  // (never read past the packed arrays)
+    const _Float16* den = (const _Float16*)a.density_out;
+    const float o[3] = {a.origins[3 * (size_t)r], a.origins[3 * (size_t)r + 1], a.origins[3 * (size_t)r + 2]};
+    const float d[3] = {a.directions[3 * (size_t)r], a.directions[3 * (size_t)r + 1], a.directions[3 * (size_t)r + 2]};
+    float carry = a.carry_in ? a.carry_in[r] : 0.f;
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (uint32_t c0 = 0; c0 < n; c0 += 64) {
+        const uint32_t j = c0 + lane;
+        float dd = 0.f, nrm[3] = {0.f, 0.f, 0.f};
+        if (j < n) {
+            const size_t s = base + j;
+            const float sigma = __expf((float)den[s * a.density_stride]);
+            dd = ngp_optical_step(sigma, a.dt[s]);
+            const float ts = a.t[s];
+            float g[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float x = (o[k] + d[k] * ts - a.aabb_lo) * aabb_inv_size;
+                g[k] = (x > 0.f && x < 1.f) ? a.dx01[3 * s + k] * aabb_inv_size : 0.f;
+            }
+            const float inv = -1.f / (sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) + 1e-10f);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) nrm[k] = g[k] * inv;
+        }
+        const float incl = wave_incl_scan(dd, lane) + carry;
+        const float T = __expf(-(incl - dd));
+        const float w = (j < n) ? (1.f - __expf(-dd)) * T : 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) acc[k] += wave_sum(w * nrm[k]);
+        carry = nvo_wave_bcast(incl, 63);
+    }
+    if (lane < 3) {
+        const float v = lane == 0 ? acc[0] : (lane == 1 ? acc[1] : acc[2]);
+        float* dst = a.out_normal + 3 * (size_t)r + lane;
+        *dst = (a.accumulate ? *dst : 0.f) + v;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -561,6 +619,36 @@ int nvo_fill_i32(nvo_stream_t stream, uint32_t n, int32_t* ptr, int32_t value) {
     NVO_REQUIRE(n == 0 || ptr, "fill_i32: NULL argument");
     if (n == 0) return NVO_OK;
     NVO_LAUNCH(k_fill_i32, dim3(nvo_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, n, ptr, value);
+    NVO_CHECK_LAUNCH();
+    return NVO_OK;
+}
+
+int nvo_ngp_normal_seed(nvo_stream_t stream, uint32_t n, float seed, void* d_density_out) {
+    NVO_REQUIRE(n == 0 || d_density_out, "ngp_normal_seed: NULL argument");
+    NVO_REQUIRE(((uintptr_t)d_density_out & 15u) == 0u, "ngp_normal_seed: rows must be 16-byte aligned");
+    const _Float16 h = (_Float16)seed;
+    NVO_REQUIRE(seed > 0.f && (float)h == seed, "ngp_normal_seed: the seed must be a positive value fp16 holds exactly");
+    if (n == 0) return NVO_OK;
+    uint16_t bits;
+    __builtin_memcpy(&bits, &h, sizeof(bits));
+    NVO_PROF(stream, "ngp_normal_seed");
+    NVO_LAUNCH(k_ngp_normal_seed, dim3(nvo_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, n, (uint32_t)bits,
+               (uint4*)d_density_out);
+    NVO_CHECK_LAUNCH();
+    return NVO_OK;
+}
+
+int nvo_ngp_composite_normals(nvo_stream_t stream, const nvo_ngp_normal_args* args) {
+    NVO_REQUIRE(args != nullptr, "ngp_composite_normals: args is NULL");
+    const nvo_ngp_normal_args a = *args;
+    NVO_REQUIRE(a.R == 0 || (a.counts && a.offsets && a.t && a.dt && a.density_out && a.dx01 && a.origins && a.directions &&
+                             a.out_normal && a.density_stride >= 1),
+                "ngp_composite_normals: NULL argument");
+    NVO_REQUIRE(a.aabb_hi > a.aabb_lo, "ngp_composite_normals: empty box");
+    if (a.R == 0) return NVO_OK;
+    NVO_PROF(stream, "ngp_composite_normals");
+    NVO_LAUNCH(k_ngp_composite_normals, dim3(nvo_div_up(a.R, 4)), dim3(256), 0, (hipStream_t)stream, a,
+               1.0f / (a.aabb_hi - a.aabb_lo));
     NVO_CHECK_LAUNCH();
     return NVO_OK;
 }

@@ -273,7 +273,8 @@ class EvaluationRenderer:
         the mapped corners (``mesh/mesh_from_nerf_raw.ply``: the density iso-surface at 1/64 m for the occupancy-grid
         back-end, the Poisson reconstruction of the oriented cloud for the nerfstudio back-end, which takes ``kwargs``), and
         that mesh, mapped back by matrix_pred2gt_scaled and cropped to the ground-truth box, is ``mesh/mesh_from_nerf.ply``;
-        vertex colours of the raw file, when it has them, are kept.  Open3D's transform and crop are
+        vertex colours of the raw file, when it has them, are kept, and so are its vertex normals (the occupancy-grid
+        renderer's ``vertex_attributes=True``), rotated by ``rotate_normals``.  Open3D's transform and crop are
         meshing.transform_mesh / crop_mesh here (parity with Open3D unpinned)."""
         from .meshing import crop_mesh, read_mesh, transform_mesh, write_mesh
 
@@ -289,7 +290,7 @@ class EvaluationRenderer:
         resolution = ((upper - lower) * self.pred2gt_transformation["scale_pred2gt"] / voxel_size).astype(int)
         file_raw = f"{self.dir_prediction}/mesh/mesh_from_nerf_raw.ply"
         self.nerf.render_mesh(file_mesh=file_raw, resolution=resolution, lower_bound=lower, upper_bound=upper, **kwargs)
-        vertices, faces, colors = read_mesh(file_raw)[:3]
+        vertices, faces, colors, normals = read_mesh(file_raw)
         vertices, faces, keep = crop_mesh(transform_mesh(vertices, matrix), faces, lower_gt, upper_gt)
         if vertices.shape[0] == 0 or faces.shape[0] == 0:
             raise RuntimeError(
@@ -298,7 +299,9 @@ class EvaluationRenderer:
                 "iso-surface threshold there (thresh of compute_and_save_marching_cubes_mesh, 2.5 by default) -- train longer or "
                 "extract at a lower thresh (a Poisson mesh: every vertex was trimmed, or the cloud is empty there)")
         file_mesh = f"{self.dir_prediction}/mesh/mesh_from_nerf.ply"
-        write_mesh(file_mesh, vertices, faces, colors=None if colors is None else colors[keep])
+        if normals is not None:  # (a raw file written with vertex_attributes: rotated the way the cloud's normals are)
+            normals = rotate_normals(normals[keep], matrix, self.pred2gt_transformation["scale_pred2gt"])
+        write_mesh(file_mesh, vertices, faces, colors=None if colors is None else colors[keep], normals=normals)
         return file_mesh
 
     def render_point_cloud(self, num_points: int = 33554432, **kwargs) -> str:
@@ -316,8 +319,9 @@ class EvaluationRenderer:
         if not callable(getattr(self.nerf, "render_point_cloud", None)):
             raise NotImplementedError(
                 f"render_point_cloud: {type(self.nerf).__name__} has no render_point_cloud(file_point_cloud, lower_bound, "
-                "upper_bound, num_points).  The nerfstudio back-end has one (NerfstudioRenderer.render_point_cloud); the "
-                "occupancy-grid back-end predicts no normals, and estimating them from neighbours is not built")
+                "upper_bound, num_points).  Both back-ends have one (NerfstudioRenderer.render_point_cloud: predicted normals; "
+                "InstantNGPRenderer.render_point_cloud: rendered density-gradient normals); a renderer that predicts no normals "
+                "cannot orient a cloud, and estimating them from neighbours is not built")
         os.makedirs(f"{self.dir_prediction}/pointcloud", exist_ok=True)
         lower_gt, upper_gt, matrix, lower, upper = self._ground_truth_box_in_model_frame()
         file_raw = f"{self.dir_prediction}/pointcloud/pointcloud_from_nerf_raw.ply"

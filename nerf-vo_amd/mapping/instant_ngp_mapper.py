@@ -138,12 +138,130 @@ class InstantNGPRenderer(NeRFRenderer):
         return self.ngp.render(width=camera_intrinsics["width"], height=camera_intrinsics["height"], spp=1,
                                linear=True)[..., 0]
 
-    def render_mesh(self, file_mesh: str, resolution, lower_bound, upper_bound) -> None:
-        """ref: evaluation/nerf_renderer.py:296-300"""
+    def render_mesh(self, file_mesh: str, resolution, lower_bound, upper_bound, vertex_attributes: bool = False) -> None:
+        """ref: evaluation/nerf_renderer.py:296-300.  ``vertex_attributes``: the file also carries vertex normals and
+        colours (pyngp.Testbed.compute_and_save_marching_cubes_mesh)."""
         from .. import pyngp
 
         bounding_box = pyngp.BoundingBox(lower_bound, upper_bound)
-        self.ngp.compute_and_save_marching_cubes_mesh(file_mesh, resolution, bounding_box)
+        if vertex_attributes:
+            self.ngp.compute_and_save_marching_cubes_mesh(file_mesh, resolution, bounding_box, vertex_attributes=True)
+        else:
+            self.ngp.compute_and_save_marching_cubes_mesh(file_mesh, resolution, bounding_box)
+
+    def render_frame_normal(self, camera_intrinsics: dict, camera_extrinsics: np.ndarray) -> np.ndarray:
+        """float32 [H, W, 3]: the rendered unit density-gradient normal of every pixel in world axes (``camera_extrinsics``
+        in the standard convention of ``render_frame``), zero where the accumulation is 0.  From the testbed's Normals
+        mode: un-premultiplied, ``2 x - 1``, re-normalised.  Parity with upstream's picture of that mode is unpinned."""
+        self._set_rendering_defaults(camera_intrinsics)
+        self._set_camera_extrinsics(camera_extrinsics)
+        self.ngp.render_mode = pyngp.Normals
+        out = self.ngp.render(width=camera_intrinsics["width"], height=camera_intrinsics["height"], spp=1, linear=True)
+        acc = out[..., 3:4]
+        hit = acc > 0
+        n = 2.0 * np.divide(out[..., 0:3], acc, out=np.full_like(out[..., 0:3], 0.5), where=hit) - 1.0
+        n = n / np.maximum(np.linalg.norm(n, axis=-1, keepdims=True), 1e-20)
+        return np.where(hit, n, 0.0).astype(np.float32)
+
+    @torch.no_grad()
+    def _generate_point_cloud(self, lower_bound, upper_bound, num_points: int, min_accumulation, seed: int) -> dict:
+        """``renderer.generate_point_cloud``'s rule over the occupancy-grid engine: random pixels
+        ``floor(rand(R, 3) * [n_active, H, W])`` of the active training frames from a generator of its own seeded with
+        ``seed``, through the testbed's training poses with the learnt corrections (``get_camera_extrinsics``); every batch
+        goes through ``NgpEngine.render_rays(normals=True)``.  ``point = origin + direction * depth`` per component in
+        float32 (unit directions, depth = the distance along them), mapped from the engine's frame to the dataset's;
+        colour by ``render_frame_color``'s rule (un-premultiply, sRGB transfer, clip, ``* 255 + 0.5``); ``normal = 2 n - 1``
+        re-normalised.  A point is kept when ``accumulation > min_accumulation`` and ``lower < point < upper`` strictly on
+        every axis; batches are appended in order until ``num_points`` are kept, the last one cut to fit, with the
+        nerfstudio path's give-up rules."""
+        from .cameras import Cameras, CameraType
+        from .renderer import POINT_CLOUD_EMPTY_BATCHES, POINT_CLOUD_MIN_SHARE
+
+        num_points = int(num_points)
+        if num_points < 1:
+            raise ValueError("render_point_cloud: num_points must be positive")
+        tb = self.ngp
+        eng = tb._engine
+        if eng is None:
+            raise RuntimeError("render_point_cloud: no network has been trained or loaded")
+        dev = tb.device
+        n_active = int(tb.nerf.training.n_images_for_training)
+        if n_active < 1:
+            raise ValueError("render_point_cloud: no active training frames")
+        poses = np.stack([self.get_camera_extrinsics(i) for i in range(n_active)])[:, :3, :4].copy()
+        poses[:, 0:3, 1:3] *= -1  # standard -> NeRF / OpenGL, the engine's camera convention (translation in its frame)
+        H, W = tb._resolution
+        intr = tb._intrinsics[:n_active]
+        cameras = Cameras(camera_to_worlds=torch.tensor(poses, dtype=torch.float32, device=dev), fx=intr[:, 0].contiguous(),
+                          fy=intr[:, 1].contiguous(), cx=intr[:, 2].contiguous(), cy=intr[:, 3].contiguous(), width=W, height=H, camera_type=CameraType.PERSPECTIVE)
+        rays_per_batch = min(pyngp._MAX_BUNDLE_RAYS, max(4096, 1 << (num_points - 1).bit_length()))
+        scale_n, off_n = float(tb._nerf_scale), torch.as_tensor(np.asarray(tb._nerf_offset), dtype=torch.float32, device=dev)
+        lower = torch.as_tensor(np.asarray(lower_bound, dtype=np.float64).reshape(3)).to(dev, torch.float32)
+        upper = torch.as_tensor(np.asarray(upper_bound, dtype=np.float64).reshape(3)).to(dev, torch.float32)
+        generator = torch.Generator(device=dev)
+        generator.manual_seed(int(seed))
+        scale = torch.tensor([n_active, H, W], device=dev)
+        parts = {"points": [], "normals": [], "view_directions": [], "colors": []}
+        kept_total, rays_total, empty = 0, 0, 0
+        while kept_total < num_points:
+            pixels = torch.floor(torch.rand((rays_per_batch, 3), device=dev, generator=generator) * scale).long()
+            bundle = cameras.generate_rays(camera_indices=pixels)
+            origins, directions = bundle.origins.reshape(-1, 3).contiguous(), bundle.directions.reshape(-1, 3).contiguous()
+            out = eng.render_rays(origins, directions, bundle.metadata["directions_norm"].reshape(-1).contiguous(), 1e-4, True)
+            points = ((origins + directions * out["depth"]) - off_n) / scale_n
+            keep = ((points > lower) & (points < upper)).all(dim=1)
+            if min_accumulation is not None:
+                keep &= out["accumulation"][:, 0] > float(min_accumulation)
+            index = keep.nonzero().flatten()[:num_points - kept_total]
+            rays_total += rays_per_batch
+            if index.numel() == 0:
+                empty += 1
+                if empty >= POINT_CLOUD_EMPTY_BATCHES:
+                    raise RuntimeError(
+                        f"render_point_cloud: {empty} consecutive batches of {rays_per_batch} rays left no point inside the box "
+                        f"{lower.tolist()} .. {upper.tolist()}; {kept_total} of {rays_total} rays were kept so far -- the field "
+                        "is empty there (train longer), or the box is not in the dataset's frame")
+                continue
+            empty = 0
+            if rays_total >= POINT_CLOUD_EMPTY_BATCHES * rays_per_batch and (kept_total + int(index.numel())) * POINT_CLOUD_MIN_SHARE < rays_total:
+                raise RuntimeError(
+                    f"render_point_cloud: only {kept_total + int(index.numel())} of {rays_total} rays gave a point inside the box "
+                    f"{lower.tolist()} .. {upper.tolist()} (fewer than 1 in {POINT_CLOUD_MIN_SHARE}): check the box, or ask for "
+                    "fewer points")
+            normal = 2.0 * out["normals"][index] - 1.0
+            acc = out["accumulation"][index]
+            lin = torch.where(acc != 0, out["rgb"][index] / acc, torch.zeros_like(acc))
+            srgb = torch.where(lin > 0.0031308, 1.055 * lin.clamp_min(1e-12) ** (1.0 / 2.4) - 0.055, 12.92 * lin)
+            parts["points"].append(points[index])
+            parts["normals"].append(normal / torch.linalg.norm(normal, dim=1, keepdim=True).clamp_min(1e-20))
+            parts["view_directions"].append(directions[index])
+            parts["colors"].append((srgb.clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8))
+            kept_total += int(index.numel())
+        return {k: torch.cat(v) for k, v in parts.items()}
+
+    def render_point_cloud(self, file_point_cloud: str, lower_bound, upper_bound, num_points: int = 33554432,
+                           remove_outliers: bool = True, std_ratio: float = 10.0, min_accumulation: float | None = 0.5,
+                           seed: int = 0) -> dict:
+        """``NerfstudioRenderer.render_point_cloud`` for this back-end -- same contract, file layout (binary .ply with
+        ``x y z nx ny nz red green blue`` and no faces) and return value: the cloud of ``_generate_point_cloud`` with the
+        field's rendered density-gradient normals, cleaned by ``remove_statistical_outlier(nb_neighbors=20, std_ratio)``,
+        normals turned towards the cameras (``orient_normals_towards_cameras``)."""
+        from ..meshing import write_mesh
+        from ..pointcloud import remove_statistical_outlier
+        from .renderer import orient_normals_towards_cameras
+
+        cloud = self._generate_point_cloud(lower_bound, upper_bound, num_points, min_accumulation, seed)
+        points, normals, colors, views = cloud["points"], cloud["normals"], cloud["colors"], cloud["view_directions"]
+        generated = int(points.shape[0])
+        if remove_outliers:
+            points, index = remove_statistical_outlier(points, nb_neighbors=20, std_ratio=std_ratio)
+            normals, colors, views = normals[index], colors[index], views[index]
+        normals = orient_normals_towards_cameras(normals, views)
+        out = {"points": points.cpu(), "normals": normals.cpu(), "colors": colors.cpu(), "view_directions": views.cpu(),
+               "generated": generated, "kept": int(points.shape[0])}
+        write_mesh(file_point_cloud, out["points"], torch.zeros(0, 3, dtype=torch.int64), colors=out["colors"],
+                   normals=out["normals"])
+        return out
 
     def _set_rendering_defaults(self, camera_intrinsics: dict) -> None:
         self.ngp.nerf.sharpen = 0.0

@@ -587,7 +587,9 @@ class NgpEngine:
         ws["ray_state_on"] = True
         ws["x01_ready"] = True
 
-    def _shade(self, ws, training: bool, stream) -> None:
+    def _shade(self, ws, training: bool, stream, keep_dydx: bool = False) -> None:
+        """``keep_dydx`` (the normals path, which has switched prepare_input_gradients on around this call and the backward
+        behind it): the inference forward stores d(encoded)/d(position) and leaves the option alone."""
         cfg = self.cfg
         R, cap = ws["R"], ws.get("n_launch", ws["cap"])
         lo, hi = cfg.aabb
@@ -597,7 +599,7 @@ class NgpEngine:
             _call("nvo_ngp_positions", stream, cap, _ptr(ws["ray_idx"]), _ptr(ws["t"]), _ptr(ws["origins"]),
                   _ptr(ws["directions"]), lo, hi, _ptr(ws["x01"]))
         # (inference needs no d(encoded)/d(position) from the forward; the option is read at launch time)
-        no_dydx = (not training) and bool(cfg.optimize_extrinsics)
+        no_dydx = (not training) and bool(cfg.optimize_extrinsics) and not keep_dydx
         if no_dydx:
             self.density_net.set_option("prepare_input_gradients", 0)
         try:
@@ -1141,9 +1143,129 @@ class NgpEngine:
         ws = self._wss[True]  # (the training workspace: an inference call in between has its own)
         return int(ws["totals"][1].item()) if ws is not None else 0
 
+    # dL/d(density pre-activation) the normals chain starts from (nvo_ngp_normal_seed).  The chain stores two 16-bit
+    # quantities behind it -- the hidden layer's gradient and dL/d(encoded) = seed * W1^T relu'(.) W2[0] -- whose size is
+    # the seed times the network's gain, about 0.1 with Xavier weights and rarely outside 1e-2 .. 1e1 once trained.  fp16
+    # keeps full precision between 6.1e-5 and 65504, whose geometric mean is 2: 16 puts the typical value there, with a
+    # factor of 4e3 to overflow and 3e4 to the subnormal range on either side.
+    NORMAL_SEED = 16.0
+
+    def _normal_buffers(self, ws) -> None:
+        """What the normals path adds to the inference workspace, on first use: the seeded dL/d(density_out) rows, the
+        position gradients, the per-ray sums -- and a ctx with room for d(encoded)/d(position) where the workspace was
+        sized without it."""
+        if "out_normal" in ws:
+            return
+        dev, cap = self.device, ws["cap"]
+        ws["d_density_out"] = torch.zeros(cap, 16, dtype=torch.float16, device=dev)
+        ws["dx01"] = torch.zeros(cap, 3, dtype=torch.float32, device=dev)
+        if not self._pig:
+            self.density_net.set_option("prepare_input_gradients", 1)
+            try:
+                ws["ctx"] = torch.empty(self.density_net.ctx_bytes(cap), dtype=torch.uint8, device=dev)
+            finally:
+                self.density_net.set_option("prepare_input_gradients", 0)
+        ws["_per_ray"]["out_normal"] = torch.zeros(ws["R_cap"], 3, dtype=torch.float32, device=dev)
+        self._ray_views(ws, ws["R"])
+
+    def _input_gradients(self, stream, n: int, x01, density_out, d_density_out, ctx, dx01, params_half) -> None:
+        """d(NORMAL_SEED * pre-activation) / d(x01) of the first n rows (a multiple of 16) into dx01, behind a forward of the
+        same n rows on the same ctx that ran with prepare_input_gradients on: seed, then nvo_bwd with dL_dparams = NULL.
+        (With NULL the backward writes no parameter gradient, raises no overflow flag, builds no live-row list and needs
+        no L1 partials -- api.hip, NwieModule::bwd_on: every range the option external_zero hands to the step's zero
+        launch is touched under `dparams` only -- so there is nothing to clear, and a training step in between sees none
+        of it.  dL/d(encoded) lands in the ctx, dx01 is overwritten.)"""
+        _call("nvo_ngp_normal_seed", stream, n, float(self.NORMAL_SEED), _ptr(d_density_out))
+        _call("nvo_bwd", self.density_net.handle, stream, n, _ptr(x01), self._pp("density", params_half), _ptr(density_out),
+              _ptr(d_density_out), _ptr(ctx), _ptr(dx01), None)
+
     @torch.no_grad()
-    def render_rays(self, origins, directions, directions_norm, min_transmittance=None):
+    def density_gradient_at(self, positions: torch.Tensor):
+        """(density [M], gradient [M, 3]) at positions of the engine's normalised frame, with the inference weights: the
+        density of ``density_at`` (bit for bit) and its gradient with respect to the position, from the chain the normals
+        path renders with (forward with d(encoded)/d(position) stored, nvo_ngp_normal_seed, nvo_bwd without a parameter
+        gradient), divided by the seed and multiplied by the density (d exp(x) = exp(x) dx; the clamp of the activation
+        at 15 is not differentiated, so the direction survives it).  A coordinate that is not strictly inside the scene box
+        has a zero derivative (the clamp of the network input, the mask of nvo_ngp_positions_bwd); points outside the box
+        give density 0 and gradient 0."""
+        cfg = self.cfg
+        lo, hi = cfg.aabb
+        stream = _stream(self.device)
+        M = positions.shape[0]
+        chunk = 1 << 18
+        net = self.density_net
+        x01 = torch.empty(chunk, 3, device=self.device)
+        out = torch.empty(chunk, 16, dtype=torch.float16, device=self.device)
+        d_out = torch.empty(chunk, 16, dtype=torch.float16, device=self.device)
+        dx = torch.empty(chunk, 3, device=self.device)
+        den = torch.empty(M, device=self.device)
+        grad = torch.empty(M, 3, device=self.device)
+        ph = self.inference_params_half()
+        if not self._pig:
+            net.set_option("prepare_input_gradients", 1)
+        try:
+            ctx = torch.empty(net.ctx_bytes(chunk), dtype=torch.uint8, device=self.device)
+            for c0 in range(0, M, chunk):
+                p = positions[c0:c0 + chunk].to(self.device, torch.float32)
+                n = p.shape[0]
+                den[c0:c0 + n] = self._density_of(p, n, x01, out, ctx, ph, stream)
+                self._input_gradients(stream, chunk, x01, out, d_out, ctx, dx, ph)
+                u = (p - lo) / (hi - lo)
+                inside = ((p >= lo) & (p <= hi)).all(dim=1, keepdim=True)
+                g = dx[:n] * (1.0 / (self.NORMAL_SEED * (hi - lo)))
+                g = torch.where((u > 0.0) & (u < 1.0) & inside, g, torch.zeros((), device=self.device))
+                grad[c0:c0 + n] = g * den[c0:c0 + n, None]
+        finally:
+            if not self._pig:
+                net.set_option("prepare_input_gradients", 0)
+        return den, grad
+
+    @torch.no_grad()
+    def color_at(self, positions: torch.Tensor, view_directions: torch.Tensor) -> torch.Tensor:
+        """Linear rgb [M, 3] the colour head gives at positions [M, 3] of the engine's normalised frame for a viewer
+        looking along ``view_directions`` [M, 3] (unit vectors, the direction a ray through the point would travel), with
+        the inference weights: the per-sample colour the compositing pass blends (logistic of the head's output).  The
+        launches of ``_shade`` with every point a ray of its own; not on the training or render path."""
+        lo, hi = self.cfg.aabb
+        stream = _stream(self.device)
+        dev = self.device
+        M = positions.shape[0]
+        chunk = 1 << 18
+        x01 = torch.empty(chunk, 3, device=dev)
+        dirs = torch.zeros(chunk, 3, device=dev)
+        dirs01 = torch.empty(chunk, 3, device=dev)
+        sh = torch.empty(chunk, 16, dtype=torch.float16, device=dev)
+        den = torch.empty(chunk, 16, dtype=torch.float16, device=dev)
+        rgb = torch.empty(chunk, 16, dtype=torch.float16, device=dev)
+        ray_idx = torch.arange(chunk, dtype=torch.int32, device=dev)
+        ctx = torch.empty(self.density_net.ctx_bytes(chunk), dtype=torch.uint8, device=dev)
+        ph = self.inference_params_half()
+        res = torch.empty(M, 3, device=dev)
+        for c0 in range(0, M, chunk):
+            p = positions[c0:c0 + chunk].to(dev, torch.float32)
+            n = p.shape[0]
+            x01.zero_()
+            x01[:n] = ((p - lo) / (hi - lo)).clamp_(0.0, 1.0)
+            dirs[:n] = view_directions[c0:c0 + n].to(dev, torch.float32)
+            _call("nvo_fwd", self.density_net.handle, stream, chunk, _ptr(x01), self._pp("density", ph), _ptr(den), _ptr(ctx))
+            _call("nvo_dirs01", stream, 3 * chunk, _ptr(dirs), _ptr(dirs01))
+            _call("nvo_sh_encode", stream, chunk, 4, _ptr(dirs01), _ptr(sh))
+            ra = _lib.NgpRgbArgs(capacity=chunk, sh=sh.data_ptr(), density_out=den.data_ptr(), ray_idx=ray_idx.data_ptr(),
+                                 weights=self._pp("rgb", ph).value, rgb_out=rgb.data_ptr(), hidden=None, d_rgb_out=None,
+                                 d_density_out=None, d_density_pre=None, d_weights=None, nonfinite_flag=None, dw_replicas=None,
+                                 n_dw_replicas=0)
+            _call("nvo_ngp_rgb_fwd", stream, C.byref(ra))
+            res[c0:c0 + n] = torch.sigmoid(rgb[:n, :3].float())
+        return res
+
+    @torch.no_grad()
+    def render_rays(self, origins, directions, directions_norm, min_transmittance=None, normals: bool = False):
         """rgb / depth / accumulation of a ray bundle with the inference weights.
+
+        ``normals``: the result gains "normals" [R, 3] -- the rendered density-gradient normal sum_i w_i n_i with the
+        colour's own weights, n_i = -grad / (|grad| + 1e-10) per sample, normalised the same way and stored as (n + 1) / 2
+        (NerfactoEngine.render_image(normals=True)'s convention; exactly 0.5 where nothing was hit).  False launches what
+        the function launched before the option existed.
 
         ``min_transmittance`` (default NgpConfig.render_min_transmittance) > 0: two rounds -- the first
         ``render_first_round`` samples of every ray are shaded and composited, then only the rays whose transmittance is
@@ -1154,6 +1276,8 @@ class NgpEngine:
         cfg = self.cfg
         R = origins.shape[0]
         ws = self._workspace(R, False)
+        if normals:
+            self._normal_buffers(ws)
         ws["origins"].copy_(origins)
         ws["directions"].copy_(directions)
         ws["directions_norm"].copy_(directions_norm.reshape(-1))
@@ -1166,32 +1290,56 @@ class NgpEngine:
         if R > 1 and found > ws["cap"]:
             h = R // 2
             dn = directions_norm.reshape(-1)
-            a = self.render_rays(origins[:h].contiguous(), directions[:h].contiguous(), dn[:h].contiguous(), min_t)
-            b = self.render_rays(origins[h:].contiguous(), directions[h:].contiguous(), dn[h:].contiguous(), min_t)
+            a = self.render_rays(origins[:h].contiguous(), directions[:h].contiguous(), dn[:h].contiguous(), min_t, normals)
+            b = self.render_rays(origins[h:].contiguous(), directions[h:].contiguous(), dn[h:].contiguous(), min_t, normals)
             self.last_render_samples = found
             return {k: torch.cat([a[k], b[k]]) for k in a}
-        self._shade_and_composite(ws, found, stream, None, ws["carry"] if min_t > 0.0 else None, False)
+        self._shade_and_composite(ws, found, stream, None, ws["carry"] if min_t > 0.0 else None, False, normals)
         if min_t > 0.0:
             # the rays that go on: not yet opaque, still inside the scene box
             alive = (ws["t_next"] >= 0.0) & (ws["carry"] < -math.log(min_t))
             resume = torch.where(alive, ws["t_next"], torch.full_like(ws["t_next"], -1.0))
             if bool(alive.any().item()):
-                self.last_render_samples = max(found, self._render_second_round(ws, resume, 0, R, stream))
-        return {"rgb": ws["out_rgb"].clamp(0, 1), "depth": ws["out_depth"].clone()[:, None],
-                "accumulation": ws["out_accumulation"].clone()[:, None]}
+                self.last_render_samples = max(found, self._render_second_round(ws, resume, 0, R, stream, normals))
+        res = {"rgb": ws["out_rgb"].clamp(0, 1), "depth": ws["out_depth"].clone()[:, None],
+               "accumulation": ws["out_accumulation"].clone()[:, None]}
+        if normals:
+            # (oracle/rays.py::render_normals_shaded: n = S / (|S| + 1e-10), stored as (n + 1) / 2)
+            S = ws["out_normal"]
+            res["normals"] = (S / (torch.linalg.norm(S, dim=-1, keepdim=True) + 1e-10) + 1.0) / 2.0
+        return res
 
-    def _shade_and_composite(self, ws, found: int, stream, carry_in, carry_out, accumulate: bool) -> None:
+    def _shade_and_composite(self, ws, found: int, stream, carry_in, carry_out, accumulate: bool, normals: bool = False) -> None:
         # the packed samples sit at the front of the workspace: the shading launches cover them, not the whole capacity
         ws["n_launch"] = min(ws["cap"], max(4096, (found + 4095) // 4096 * 4096))
         self.render_shaded_total += found  # (running count of the samples inference has shaded: diagnostics, tests)
+        # (the normals path: the forward stores d(encoded)/d(position), and the option stays on until the backward has read
+        # it -- setting it either way invalidates the stored block; afterwards it is what it was)
+        switch = normals and not self._pig
+        if switch:
+            self.density_net.set_option("prepare_input_gradients", 1)
         try:
-            self._shade(ws, False, stream)
+            self._shade(ws, False, stream, keep_dydx=normals)
             la = self._loss_args(ws, False, False, None, carry_in, carry_out, accumulate)
             _call("nvo_ngp_composite_loss", stream, C.byref(la))
+            if normals:
+                n = ws["n_launch"]
+                self._input_gradients(stream, n, ws["x01"], ws["density_out"], ws["d_density_out"], ws["ctx"], ws["dx01"],
+                                      self._fwd_half)
+                lo, hi = self.cfg.aabb
+                na = _lib.NgpNormalArgs(
+                    R=ws["R"], capacity=n, counts=ws["counts"].data_ptr(), offsets=ws["offsets"].data_ptr(),
+                    t=ws["t"].data_ptr(), dt=ws["dt"].data_ptr(), density_out=ws["density_out"].data_ptr(), density_stride=16,
+                    dx01=ws["dx01"].data_ptr(), origins=ws["origins"].data_ptr(), directions=ws["directions"].data_ptr(),
+                    aabb_lo=lo, aabb_hi=hi, carry_in=None if carry_in is None else carry_in.data_ptr(),
+                    accumulate=int(bool(accumulate)), out_normal=ws["out_normal"].data_ptr())
+                _call("nvo_ngp_composite_normals", stream, C.byref(na))
         finally:
             del ws["n_launch"]
+            if switch:
+                self.density_net.set_option("prepare_input_gradients", 0)
 
-    def _render_second_round(self, ws, resume, lo: int, hi: int, stream) -> int:
+    def _render_second_round(self, ws, resume, lo: int, hi: int, stream, normals: bool = False) -> int:
         """The rest of the march for the alive rays lo .. hi - 1 of the bundle (the others sit the launch out), added to the
         first round's outputs; halves of the range when the samples do not fit.  Returns the largest sample count a launch
         of this round held."""
@@ -1202,8 +1350,8 @@ class NgpEngine:
         found = int(ws["totals"][0].item())
         if found > ws["cap"] and hi - lo > 1:
             mid = (lo + hi) // 2
-            return max(self._render_second_round(ws, resume, lo, mid, stream),
-                       self._render_second_round(ws, resume, mid, hi, stream))
+            return max(self._render_second_round(ws, resume, lo, mid, stream, normals),
+                       self._render_second_round(ws, resume, mid, hi, stream, normals))
         if found > 0:
-            self._shade_and_composite(ws, found, stream, ws["carry"], None, True)
+            self._shade_and_composite(ws, found, stream, ws["carry"], None, True, normals)
         return found

@@ -83,6 +83,7 @@ class RenderMode(enum.Enum):
 
 Shade = RenderMode.Shade
 Depth = RenderMode.Depth
+Normals = RenderMode.Normals
 
 
 class BoundingBox:
@@ -182,7 +183,7 @@ class Testbed:
         self._camera = np.eye(4)[:3][_TO_NGP_ROWS]
         self._generator = torch.Generator(device=self.device)
         self._draw_scale = None
-        self._render_cache = None  # (key, rgba [n,4], z-depth [n]) of the last rendered view
+        self._render_cache = None  # (key, rgba [n,4], z-depth [n], normals [n,3] | None) of the last rendered view
         self._generator.manual_seed(42)
 
     # ---- dataset / network set-up ------------------------------------------------------------------------
@@ -359,15 +360,20 @@ class Testbed:
         """float32 [height, width, 4].  Shade: alpha-premultiplied linear RGB + alpha (the reference divides by
         alpha, nerf_renderer.py:274-277); Depth: z-depth in every channel (it reads channel 0, :296).  Pinhole with
         the focal length of ``fov`` along ``fov_axis``, square pixels and a centred principal point, like the
-        testbed's free camera.  (rays_per_chunk = 0: bundles sized so that the samples their rays find fill ~85 % of the
+        testbed's free camera.  Normals: channels 0-2 are ``(n + 1) / 2 * accumulation`` with n the rendered unit
+        density-gradient normal in world axes (NgpEngine.render_rays(normals=True)), premultiplied like Shade's colour,
+        channel 3 the accumulation; upstream's exact shading of this mode is not on disk -- [UPSTREAM] unpinned.  All
+        modes come from one cached pass; a pass made for Shade or Depth is repeated with normals when Normals is asked
+        for first, and then serves the other two with the same bits.  (rays_per_chunk = 0: bundles sized so that the samples their rays find fill ~85 % of the
         inference capacity -- from the training batches' samples per ray at first, from the previous bundle's afterwards; a
         bundle that still finds more than fit is rendered in halves by NgpEngine.render_rays, no ray is dropped.)"""
         if self._engine is None:
             raise RuntimeError("render: no network has been trained or loaded")
         if not linear:
             raise NotImplementedError("render(linear=False): the reference always asks for linear output")
-        if self.render_mode not in (Shade, Depth):
-            raise NotImplementedError(f"render_mode {self.render_mode}: the reference uses Shade and Depth")
+        if self.render_mode not in (Shade, Depth, Normals):
+            raise NotImplementedError(f"render_mode {self.render_mode}: Shade, Depth and Normals are built")
+        want_normals = self.render_mode == Normals
         # The reference renders every frame twice, once per mode (evaluation/nerf_renderer.py:259-300): both modes come
         # from ONE pass over the rays, kept until the camera, the image size or the weights change.
         eng = self._engine
@@ -379,7 +385,10 @@ class Testbed:
         min_t = float(self.nerf.render_min_transmittance)  # (upstream default 0.01; the reference sets 1e-4)
         key = (self._camera.tobytes(), float(self.fov), int(self.fov_axis), int(width), int(height), int(rays_per_chunk),
                id(eng), eng.params_version, min_t)
-        if self._render_cache is None or self._render_cache[0] != key:
+        # (the last element of the cached key: whether the pass computed normals -- such a pass serves every mode)
+        cached = self._render_cache
+        if cached is None or cached[0][:-1] != key or (want_normals and not cached[0][-1]):
+            key = key + (want_normals,)
             focal = 0.5 * (width if self.fov_axis == 0 else height) / math.tan(0.5 * math.radians(self.fov))
             c2w = torch.tensor(self._camera[_FROM_NGP_ROWS], dtype=torch.float32).unsqueeze(0)
             cams = Cameras(fx=focal, fy=focal, cx=0.5 * width, cy=0.5 * height, height=height, width=width,
@@ -391,11 +400,14 @@ class Testbed:
             n = o.shape[0]
             rgba = torch.empty(n, 4, device=self.device)
             z = torch.empty(n, device=self.device)
+            nrm = torch.empty(n, 3, device=self.device) if want_normals else None
             lo = 0
             while lo < n:
                 hi = min(n, lo + rays_per_chunk)
                 nn = dn[lo:hi]
-                out = eng.render_rays(o[lo:hi].contiguous(), d[lo:hi].contiguous(), nn.contiguous(), min_t)
+                out = eng.render_rays(o[lo:hi].contiguous(), d[lo:hi].contiguous(), nn.contiguous(), min_t, want_normals)
+                if want_normals:
+                    nrm[lo:hi] = out["normals"]
                 rgba[lo:hi, :3] = out["rgb"]
                 rgba[lo:hi, 3:] = out["accumulation"]
                 z[lo:hi] = out["depth"][:, 0] / nn  # distance along the ray -> z-depth
@@ -403,15 +415,18 @@ class Testbed:
                     per_ray = max(16.0, eng.last_render_samples / (hi - lo))
                     rays_per_chunk = max(256, min(_MAX_BUNDLE_RAYS, int(0.85 * cap / per_ray) // 256 * 256))
                 lo = hi
-            self._render_cache = (key, rgba, z)
-        _, rgba, z = self._render_cache
+            self._render_cache = (key, rgba, z, nrm)
+        _, rgba, z, nrm = self._render_cache
+        if want_normals:
+            return torch.cat([nrm * rgba[:, 3:], rgba[:, 3:]], dim=1).view(height, width, 4).cpu().numpy()
         if self.render_mode == Depth:
             return z[:, None].expand(-1, 4).reshape(height, width, 4).cpu().numpy()
         shade = torch.cat([rgba[:, :3] * (2.0 ** self.exposure), rgba[:, 3:]], dim=1)
         return shade.view(height, width, 4).cpu().numpy()
 
     def compute_and_save_marching_cubes_mesh(self, filename: str, resolution=(256, 256, 256), aabb: BoundingBox | None = None,
-                                             thresh: float = 2.5, generate_uvs_for_obj_file: bool = False) -> None:
+                                             thresh: float = 2.5, generate_uvs_for_obj_file: bool = False,
+                                             vertex_attributes: bool = False) -> None:
         """Density iso-surface at ``thresh`` (instant-ngp's default 2.5) over ``aabb`` (dataset / world coordinates, as
         the reference passes it: nerf_renderer.py:296-300; empty or infinite -> the scene box; clamped to the scene box)
         sampled on a lattice of ``resolution`` samples per axis, written as .obj or .ply (positions only: 12 bytes per
@@ -419,7 +434,15 @@ class Testbed:
         the lattice indices) and the surface extracted by the HIP extractor ``meshing.extract_isosurface`` (marching
         tetrahedra with every vertex owned by its lattice edge) instead of upstream's marching-cubes
         tables: same iso-surface, another triangulation.  Both work in the engine's normalised frame; the vertices are
-        mapped back (in float64) and written in the same dataset coordinates the box is given in."""
+        mapped back (in float64) and written in the same dataset coordinates the box is given in.
+
+        ``vertex_attributes`` (upstream's call saves vertex normals and colours with the mesh; off: the file above, byte
+        for byte): ``nx ny nz`` = ``-grad / (|grad| + 1e-10)`` of ``NgpEngine.density_gradient_at`` at the vertex -- the
+        dataset frame is the engine's scaled and shifted, axes in the same order, so the direction is written as it is
+        -- and ``red green blue`` = the colour head at the vertex seen along ``-normal`` (a viewer facing the surface
+        head-on), encoded by ``render_frame_color``'s rule (sRGB transfer, clip, ``* 255 + 0.5``).  The colour rule is the
+        project's own: upstream is believed to look outward from the cube's centre, and its source is not on disk
+        [UPSTREAM, unpinned]."""
         from .meshing import extract_isosurface, write_mesh
 
         if self._engine is None:
@@ -441,6 +464,13 @@ class Testbed:
         dens = e.density_lattice(unit_lo, unit_hi, res)
         verts, faces = extract_isosurface(dens, unit_lo, unit_hi, float(thresh))
         del dens
+        normals = colors = None
+        if vertex_attributes:
+            _, grad = e.density_gradient_at(verts)
+            normals = -grad / (torch.linalg.norm(grad, dim=1, keepdim=True) + 1e-10)
+            lin = e.color_at(verts, -normals)
+            srgb = torch.where(lin > 0.0031308, 1.055 * lin.clamp_min(1e-12) ** (1.0 / 2.4) - 0.055, 12.92 * lin)
+            colors = (srgb.clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8)
         verts = ((verts.double() - torch.as_tensor(off, device=verts.device)) / scale).float()
         os.makedirs(os.path.dirname(os.path.abspath(filename)), exist_ok=True)
-        write_mesh(filename, verts, faces)
+        write_mesh(filename, verts, faces, colors=colors, normals=normals)

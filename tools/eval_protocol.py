@@ -123,7 +123,8 @@ def _mesh_nerf_defaults(points, depth, training_pixels):
 def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, eval_frames=8, chunk=8, device="cuda:0",
         camera_optimizer_mode=None, pose_noise=None, deterministic=False, seed=42, dynamic_loss_scale=None, out_dir=None,
         quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None, mesh=False, metrics_3d=False,
-        mesh_nerf=False, pointcloud=False, pointcloud_points=33554432, poisson_depth=None, mesh_nerf_points=None):
+        mesh_nerf=False, pointcloud=False, pointcloud_points=33554432, poisson_depth=None, mesh_nerf_points=None,
+        mesh_nerf_attributes=False):
     """``method``: 'nerfstudio' (the default mapper) or 'instant-ngp' (the occupancy-grid back-end through the pyngp facade,
     /root/reference/nerf_vo/mapping/instant_ngp.py + evaluation/nerf_renderer.py:221-320; the room is shrunk by
     ``scene_scale``, default 0.5, so that it lies inside that back-end's scene box: it takes poses as they come).
@@ -131,7 +132,8 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
     iso-surface of the occupancy-grid back-end, the Poisson reconstruction (at ``poisson_depth``) of a cloud of
     ``mesh_nerf_points`` points for the nerfstudio back-end; with ``metrics_3d`` the table gains its row.  Their defaults
     are the reference's 33 554 432 points and depth 9 brought down to the protocol's small frames (``_mesh_nerf_defaults``).
-    ``pointcloud`` (nerfstudio only): also ``render_point_cloud(num_points=pointcloud_points)`` -- the oriented, coloured cloud
+    ``mesh_nerf_attributes`` (instant-ngp): the density mesh carries vertex normals and colours (``vertex_attributes``).
+    ``pointcloud`` (both back-ends): also ``render_point_cloud(num_points=pointcloud_points)`` -- the oriented, coloured cloud
     of the field, outliers removed, cropped to the ground-truth mesh's box -- and its score, results/metrics_3d_pointcloud.csv."""
     entry.build()
     from nerf_vo_amd.evaluation import (EvaluationRenderer, Evaluator2D, Evaluator3D, read_color, transform_matrices_pred2gt)
@@ -146,8 +148,8 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
     out_dir = out_dir or tempfile.mkdtemp(prefix="nvo_eval_")
     n_frames = keyframes * frame_stride  # dataset frames; every frame_stride-th one is a keyframe (configs: frame_stride 2)
     ngp = method == "instant-ngp"
-    if pointcloud and ngp:
-        raise SystemExit("--pointcloud needs --method nerfstudio (the occupancy-grid back-end predicts no normals)")
+    if mesh_nerf_attributes and not ngp:
+        raise SystemExit("--mesh-nerf-attributes needs --method instant-ngp (the nerfstudio mesh carries its colours already)")
     if ngp and abs(width / height - 1200.0 / 680.0) > 0.01:
         # (the testbed's free camera has ONE focal length, evaluation/nerf_renderer.py:152: Replica's intrinsics have square
         # pixels only at its own aspect -- 160 x 120 renders with fx != fy come out at 13 dB)
@@ -214,7 +216,7 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
     if mesh_nerf:  # run.py:72: mesh/mesh_from_nerf_raw.ply and its crop mesh/mesh_from_nerf.ply
         t_mesh = time.perf_counter()
         if ngp:
-            file_mesh = renderer.render_mesh(source="nerf")
+            file_mesh = renderer.render_mesh(source="nerf", **({"vertex_attributes": True} if mesh_nerf_attributes else {}))
         else:
             mesh_nerf_points, poisson_depth = _mesh_nerf_defaults(mesh_nerf_points, poisson_depth, keyframes * height * width)
             file_mesh = renderer.render_mesh(source="nerf", num_points=mesh_nerf_points, depth=poisson_depth)
@@ -324,7 +326,9 @@ if __name__ == "__main__":
                     "default: the reference's 9, lowered until a surface cell holds about four points")
     ap.add_argument("--mesh-nerf-points", type=int, default=None, help="nerfstudio --mesh-nerf: points of the cloud before "
                     "outlier removal; default: the reference's 33554432, at most a quarter of the training pixels")
-    ap.add_argument("--pointcloud", action="store_true", help="nerfstudio only: also export the field's oriented point cloud, "
+    ap.add_argument("--mesh-nerf-attributes", action="store_true", help="instant-ngp --mesh-nerf: the density mesh carries "
+                    "vertex normals (negated density gradient) and colours")
+    ap.add_argument("--pointcloud", action="store_true", help="also export the field's oriented point cloud, "
                     "cropped to the ground-truth mesh's box (pointcloud/pointcloud_from_nerf.ply), and score it "
                     "(results/metrics_3d_pointcloud.csv)")
     ap.add_argument("--pointcloud-points", type=int, default=33554432, help="points of the cloud before outlier removal and crop")
@@ -334,4 +338,4 @@ if __name__ == "__main__":
         dynamic_loss_scale=False if a.static_loss_scale else None, keyframe_views=not a.no_keyframe_views,
         method=a.method, scene_scale=a.scene_scale, mesh=a.mesh, metrics_3d=a.metrics_3d, mesh_nerf=a.mesh_nerf,
         pointcloud=a.pointcloud, pointcloud_points=a.pointcloud_points, poisson_depth=a.poisson_depth,
-        mesh_nerf_points=a.mesh_nerf_points)
+        mesh_nerf_points=a.mesh_nerf_points, mesh_nerf_attributes=a.mesh_nerf_attributes)
