@@ -1184,6 +1184,96 @@ typedef struct nvo_poisson_vcycle_args {
 uint64_t nvo_poisson_vcycle_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t levels);
 int nvo_poisson_vcycle(nvo_stream_t stream, const nvo_poisson_vcycle_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * M. TSDF fusion into a block-sparse volume (csrc/tsdf_blocks.hip, csrc/iso_blocks.hip): the lattice of section H cut
+ *    into blocks of NVO_TSDF_BLOCK^3 voxels, of which only those a frame's truncation band touches are allocated -- the
+ *    shape of the reference's Open3D VoxelBlockGrid.  DESIGN.md "Block-sparse TSDF volume" states the rules;
+ *    tests/helpers/tsdf_blocks_oracle.py restates the touch rule in float32 numpy, operation for operation.
+ *    Block table: int32 [tbx][tby][tbz] (z fastest; at most 2^26 entries), -1 = unallocated, else the block's id in the
+ *    pool, 0 <= id < n_allocated <= NVO_TSDF_BLOCKS_MAX_ALLOCATED.  Block (bi, bj, bk) holds the voxels 8*bi .. 8*bi+7 per
+ *    axis; voxel (i, j, k) samples lower + float(i, j, k) * voxel_size.  Pool, caller-owned, zero where never written:
+ *    tsdf [capacity][512], weight [capacity][512], color [capacity][3][512]; local index (li*8 + lj)*8 + lk.
+ *    frames, depth, rgb: as in section H.  Every table index, list entry and id is checked before it is used: an entry
+ *    that fails is skipped.  No float atomics, no allocation.
+ *      nvo_tsdf_blocks_touch      marks[t] |= 1 << f for every block t of the table that frame f < K touches (integer
+ *                                 atomic OR: order-independent).  Per pixel (ui, vi) with 0 < d <= depth_max:
+ *                                 a = (ui - cx) / fx, b = (vi - cy) / fy; samples z_n = min(z_lo + n * h, z_hi),
+ *                                 n = 0 .. n_samples - 1, z_lo = max(d - trunc, 0), z_hi = d + trunc, h = voxel_size / 2;
+ *                                 p = camera->world of (a z, b z, z); rho = (z * k_pix + (h / 2) * sqrt((a a + b b) + 1))
+ *                                 + voxel_size / 4; the blocks floor(((p - rho) - lower) / (8 voxel_size)) ..
+ *                                 floor(((p + rho) - lower) / (8 voxel_size)) per axis, cut to the table, are marked.
+ *                                 touch_frames [K][16]: camera->world 3x4 row-major, k_pix, three unused values.
+ *      nvo_tsdf_blocks_integrate  applies the frames f < K with bit f set in list_mask[e] to the block list[e] (a table
+ *                                 index; the entries must be distinct), e < n_list, in table order, by the per-voxel rule
+ *                                 of section H, expression for expression; a workgroup owns a block, a voxel's values stay
+ *                                 in registers across the frames and are stored once.
+ *      nvo_tsdf_blocks_iso_count / nvo_tsdf_blocks_iso_emit
+ *                                 the extraction of section J on the lattice [8 tbx][8 tby][8 tbz] with values = -tsdf,
+ *                                 threshold 0, valid = allocated and weight >= weight_threshold, step = voxel_size: same
+ *                                 edge ownership, case table, winding and position formula (global lattice index).
+ *                                 order [n_blocks]: table indices of the blocks to walk, ascending.  A workgroup owns
+ *                                 a block; vertex order: ascending (block in `order`, local index, edge kind); face order:
+ *                                 ascending (block, local index of the cube, tetrahedron, triangle).  count writes vrank,
+ *                                 mask, tcount [n_allocated * 512] and totals [2][n_allocated] (vertices, then triangles),
+ *                                 all indexed by block ID; the caller turns the totals, taken in `order`, into the
+ *                                 exclusive prefix sums vertex_base / face_base [n_allocated] (by id) and their sums
+ *                                 n_vertices / n_faces for emit, which also writes colors [V][3] uint8 =
+ *                                 clamp(rint((1 - t) * c_a + t * c_b), 0, 255) in fp32 as written.
+ * ---------------------------------------------------------------------------------------------- */
+#define NVO_TSDF_BLOCK 8
+#define NVO_TSDF_BLOCKS_MAX_TABLE (1u << 26)
+#define NVO_TSDF_BLOCKS_MAX_ALLOCATED (1u << 22)   /* id * 512 + local < 2^31 */
+typedef struct nvo_tsdf_blocks_args {
+    const int32_t* table;        /* [tbx][tby][tbz]; integrate */
+    float* tsdf;                 /* integrate: [n_allocated or more][512] */
+    float* weight;
+    float* color;                /* [..][3][512] */
+    const float* frames;         /* [K][16] world->camera 3x4, fx fy cx cy */
+    const float* touch_frames;   /* touch: [K][16] camera->world 3x4, k_pix = 0.5 sqrt(1/fx^2 + 1/fy^2), 3 unused */
+    const float* depth;          /* [K][H][W] */
+    const uint8_t* rgb;          /* integrate: [K][H][W][3] */
+    uint32_t* marks;             /* touch: [tbx*tby*tbz] */
+    const int32_t* list;         /* integrate: [n_list] table indices, distinct */
+    const uint32_t* list_mask;   /* integrate: [n_list] frame masks */
+    uint32_t n_list;
+    uint32_t n_allocated;        /* integrate: ids at or beyond it are skipped */
+    uint32_t tbx, tby, tbz;
+    uint32_t K, H, W;
+    uint32_t n_samples;          /* touch: samples per pixel, ceil(2 trunc / h) + 2 */
+    float lower_x, lower_y, lower_z;
+    float voxel_size;
+    float trunc;
+    float depth_max;
+} nvo_tsdf_blocks_args;
+int nvo_tsdf_blocks_touch(nvo_stream_t stream, const nvo_tsdf_blocks_args* args);
+int nvo_tsdf_blocks_integrate(nvo_stream_t stream, const nvo_tsdf_blocks_args* args);
+
+typedef struct nvo_tsdf_blocks_iso_args {
+    const int32_t* table;
+    const float* tsdf;
+    const float* weight;
+    const float* color;          /* emit only */
+    const int32_t* order;        /* [n_blocks] table indices, ascending */
+    int64_t* totals;             /* [2][n_allocated], by id: written by count */
+    uint32_t* vrank;             /* [n_allocated * 512] */
+    uint8_t* mask;               /* [n_allocated * 512] */
+    uint8_t* tcount;             /* [n_allocated * 512] */
+    const int64_t* vertex_base;  /* emit only: [n_allocated], by id */
+    const int64_t* face_base;    /* emit only: [n_allocated], by id */
+    float* vertices;             /* emit only: [n_vertices][3] */
+    uint8_t* colors;             /* emit only: [n_vertices][3] */
+    int32_t* faces;              /* emit only: [n_faces][3] */
+    uint64_t n_vertices, n_faces;
+    uint32_t n_blocks;
+    uint32_t n_allocated;
+    uint32_t tbx, tby, tbz;
+    float weight_threshold;
+    float lower[3];
+    float voxel_size;
+} nvo_tsdf_blocks_iso_args;
+int nvo_tsdf_blocks_iso_count(nvo_stream_t stream, const nvo_tsdf_blocks_iso_args* args);
+int nvo_tsdf_blocks_iso_emit(nvo_stream_t stream, const nvo_tsdf_blocks_iso_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,6 +224,27 @@ class PoissonVcycleArgs(C.Structure):
 POISSON_MAX_NODES_PER_AXIS = 4097  # NVO_POISSON_MAX_NODES_PER_AXIS
 
 
+class TsdfBlocksArgs(C.Structure):
+    """mirror of nvo_tsdf_blocks_args"""
+    _fields_ = [("table", _p), ("tsdf", _p), ("weight", _p), ("color", _p), ("frames", _p), ("touch_frames", _p), ("depth", _p),
+                ("rgb", _p), ("marks", _p), ("list", _p), ("list_mask", _p), ("n_list", _u32), ("n_allocated", _u32),
+                ("tbx", _u32), ("tby", _u32), ("tbz", _u32), ("K", _u32), ("H", _u32), ("W", _u32), ("n_samples", _u32),
+                ("lower_x", _f), ("lower_y", _f), ("lower_z", _f), ("voxel_size", _f), ("trunc", _f), ("depth_max", _f)]
+
+
+class TsdfBlocksIsoArgs(C.Structure):
+    """mirror of nvo_tsdf_blocks_iso_args"""
+    _fields_ = [("table", _p), ("tsdf", _p), ("weight", _p), ("color", _p), ("order", _p), ("totals", _p), ("vrank", _p),
+                ("mask", _p), ("tcount", _p), ("vertex_base", _p), ("face_base", _p), ("vertices", _p), ("colors", _p),
+                ("faces", _p), ("n_vertices", _u64), ("n_faces", _u64), ("n_blocks", _u32), ("n_allocated", _u32),
+                ("tbx", _u32), ("tby", _u32), ("tbz", _u32), ("weight_threshold", _f), ("lower", _f * 3), ("voxel_size", _f)]
+
+
+TSDF_BLOCK = 8                          # NVO_TSDF_BLOCK
+TSDF_BLOCKS_MAX_TABLE = 1 << 26         # NVO_TSDF_BLOCKS_MAX_TABLE
+TSDF_BLOCKS_MAX_ALLOCATED = 1 << 22     # NVO_TSDF_BLOCKS_MAX_ALLOCATED
+
+
 _SIGNATURES = {
     "nvo_last_error": (C.c_char_p, []),
     "nvo_version": (_int, []),
@@ -326,6 +347,11 @@ _SIGNATURES = {
     "nvo_poisson_residual_norm": (_int, [_p, C.POINTER(PoissonLevelArgs)]),
     "nvo_poisson_vcycle_scratch_bytes": (_u64, [_u32, _u32, _u32, _u32]),
     "nvo_poisson_vcycle": (_int, [_p, C.POINTER(PoissonVcycleArgs)]),
+    # group M
+    "nvo_tsdf_blocks_touch": (_int, [_p, C.POINTER(TsdfBlocksArgs)]),
+    "nvo_tsdf_blocks_integrate": (_int, [_p, C.POINTER(TsdfBlocksArgs)]),
+    "nvo_tsdf_blocks_iso_count": (_int, [_p, C.POINTER(TsdfBlocksIsoArgs)]),
+    "nvo_tsdf_blocks_iso_emit": (_int, [_p, C.POINTER(TsdfBlocksIsoArgs)]),
     # group E
     "nvo_adam_step": (_int, [_p, C.POINTER(AdamArgs), _u32, C.POINTER(AdamGroup), C.POINTER(AdamTail)]),
     "nvo_opt_commit": (_int, [_p, C.POINTER(OptCommitArgs), C.POINTER(StepScalars)]),

@@ -22,6 +22,7 @@
 #include "nvo_kernels.h"
 #include "../../include/nerfvo_hip.h"
 #include "iso_tables.h"
+#include "iso_dev.h"
 
 #include <math.h>
 
@@ -58,19 +59,6 @@ __device__ __forceinline__ IsoScratch iso_scratch(void* base, uint64_t n, uint64
     return s;
 }
 
-// exclusive prefix sum of v over the 256 threads and the total; lds holds 4 words and is free again on return
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* lds, uint32_t& total) {
-    const uint32_t incl = nvo_wave_incl_scan(v);
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 63u) lds[wave] = incl;
-    __syncthreads();
-    const uint32_t w0 = lds[0], w1 = lds[1], w2 = lds[2], w3 = lds[3];
-    __syncthreads();
-    total = w0 + w1 + w2 + w3;
-    const uint32_t before = (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u);
-    return before + incl - v;
-}
-
 // bit m: corner m of the cube at (i, j, k) is inside; bit 8 + m: it is in the lattice.  Corner 0 is the point itself.
 __device__ __forceinline__ uint32_t corner_bits(const nvo_iso_args& a, uint32_t p, uint32_t i, uint32_t j, uint32_t k) {
     uint32_t bits = 0;
@@ -101,13 +89,6 @@ __device__ __forceinline__ uint32_t neighbourhood(const nvo_iso_args& a, uint32_
                 nb |= (ok ? 1u : 0u) << ((dx + 1) * 9 + (dy + 1) * 3 + (dz + 1));
             }
     return nb;
-}
-
-// the cube whose minimum corner is the point minus (ox, oy, oz) is active
-__device__ __forceinline__ bool cube_active(uint32_t nb, uint32_t ox, uint32_t oy, uint32_t oz) {
-    constexpr uint32_t kCube = 1u | 2u | 8u | 16u | 512u | 1024u | 4096u | 8192u;  // offsets {0,1}^3 from the minimum corner
-    const uint32_t start = (1u - ox) * 9u + (1u - oy) * 3u + (1u - oz);
-    return ((nb >> start) & kCube) == kCube;
 }
 
 __global__ void __launch_bounds__(kBlock) k_iso_count(const nvo_iso_args a, uint32_t n, uint32_t groups) {

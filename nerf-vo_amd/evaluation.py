@@ -225,13 +225,16 @@ class EvaluationRenderer:
                                f"{self.dir_prediction}/{folder}/depth/{index:06d}.png")
         return indices
 
-    def render_mesh(self, source: str = "frames", mode: str = "evaluation_frames", **kwargs) -> str:
+    def render_mesh(self, source: str = "frames", mode: str = "evaluation_frames", volume: str = "dense", **kwargs) -> str:
         """``source='frames'``: ``mesh/mesh_from_<mode>.ply`` fused from the colour / depth files ``render_frames(mode)``
         wrote (rendered first when their folder is absent) at the ground-truth poses of those frames (renderer.py:126-164,
-        265-273): TSDF fusion on the GPU, nerf_vo_amd/tsdf.py.  ``source='nerf'``: ``mesh/mesh_from_nerf.ply``, the
+        265-273): TSDF fusion on the GPU, nerf_vo_amd/tsdf.py, into a dense volume (``volume='dense'``) or a block-sparse one
+        as the reference's (``volume='blocks'``).  ``source='nerf'``: ``mesh/mesh_from_nerf.ply``, the
         mesh of the model's field cropped to the ground-truth mesh's box (``_render_mesh_from_nerf``; ``kwargs`` go to the
         model renderer's ``render_mesh``).  Returns the file's path."""
         if source == "nerf":
+            if volume != "dense":
+                raise TypeError("render_mesh(source='nerf') takes no volume")
             return self._render_mesh_from_nerf(**kwargs)
         if kwargs:
             raise TypeError(f"render_mesh(source={source!r}) takes no further arguments, got {sorted(kwargs)}")
@@ -250,7 +253,7 @@ class EvaluationRenderer:
                   for f in sorted(os.listdir(depth_dir)) if f.endswith(".png")]
         extrinsics = np.stack([np.asarray(self.dataset.camera_extrinsics[i], dtype=np.float64) for i in indices])
         integrate_mesh(file_mesh=file_mesh, camera_intrinsics=self.dataset.camera_intrinsics, camera_extrinsics=extrinsics,
-                       frames_color=colors, frames_depth=depths)
+                       frames_color=colors, frames_depth=depths, volume=volume)
         return file_mesh
 
     def _ground_truth_box_in_model_frame(self) -> tuple:

@@ -124,8 +124,9 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
         camera_optimizer_mode=None, pose_noise=None, deterministic=False, seed=42, dynamic_loss_scale=None, out_dir=None,
         quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None, mesh=False, metrics_3d=False,
         mesh_nerf=False, pointcloud=False, pointcloud_points=33554432, poisson_depth=None, mesh_nerf_points=None,
-        mesh_nerf_attributes=False):
-    """``method``: 'nerfstudio' (the default mapper) or 'instant-ngp' (the occupancy-grid back-end through the pyngp facade,
+        mesh_nerf_attributes=False, mesh_volume="dense"):
+    """``mesh_volume``: the volume ``render_mesh(source='frames')`` fuses into, 'dense' or 'blocks' (nerf_vo_amd/tsdf.py).
+    ``method``: 'nerfstudio' (the default mapper) or 'instant-ngp' (the occupancy-grid back-end through the pyngp facade,
     /root/reference/nerf_vo/mapping/instant_ngp.py + evaluation/nerf_renderer.py:221-320; the room is shrunk by
     ``scene_scale``, default 0.5, so that it lies inside that back-end's scene box: it takes poses as they come).
     ``mesh_nerf``: also ``render_mesh(source='nerf')`` cropped to the ground-truth mesh's box (run.py:72) -- the density
@@ -209,8 +210,9 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
     mesh_info = None
     if mesh:  # the protocol's last render step (run.py:71): mesh/mesh_from_evaluation_frames.ply
         t_mesh = time.perf_counter()
-        file_mesh = renderer.render_mesh(source="frames", mode="evaluation_frames")
-        mesh_info = {"file": file_mesh if not own_dir else os.path.basename(file_mesh), "bytes": os.path.getsize(file_mesh),
+        file_mesh = renderer.render_mesh(source="frames", mode="evaluation_frames", volume=mesh_volume)
+        mesh_info = {"volume": mesh_volume, "file": file_mesh if not own_dir else os.path.basename(file_mesh),
+                     "bytes": os.path.getsize(file_mesh),
                      "seconds": time.perf_counter() - t_mesh}
     mesh_nerf_info = None
     if mesh_nerf:  # run.py:72: mesh/mesh_from_nerf_raw.ply and its crop mesh/mesh_from_nerf.ply
@@ -317,6 +319,8 @@ if __name__ == "__main__":
     ap.add_argument("--method", default="nerfstudio", choices=["nerfstudio", "instant-ngp"])
     ap.add_argument("--scene-scale", type=float, default=None)
     ap.add_argument("--mesh", action="store_true", help="also fuse the rendered evaluation frames into mesh/mesh_from_evaluation_frames.ply")
+    ap.add_argument("--mesh-volume", default="dense", choices=["dense", "blocks"], help="--mesh: fuse into the dense volume or "
+                    "into the block-sparse one (the reference's VoxelBlockGrid shape)")
     ap.add_argument("--metrics-3d", action="store_true", help="also score the mesh against the fused ground-truth mesh "
                     "(results/metrics_3d.csv); implies --mesh")
     ap.add_argument("--mesh-nerf", action="store_true", help="also the mesh of the field itself, cropped to the ground-truth mesh's "
@@ -338,4 +342,4 @@ if __name__ == "__main__":
         dynamic_loss_scale=False if a.static_loss_scale else None, keyframe_views=not a.no_keyframe_views,
         method=a.method, scene_scale=a.scene_scale, mesh=a.mesh, metrics_3d=a.metrics_3d, mesh_nerf=a.mesh_nerf,
         pointcloud=a.pointcloud, pointcloud_points=a.pointcloud_points, poisson_depth=a.poisson_depth,
-        mesh_nerf_points=a.mesh_nerf_points, mesh_nerf_attributes=a.mesh_nerf_attributes)
+        mesh_nerf_points=a.mesh_nerf_points, mesh_nerf_attributes=a.mesh_nerf_attributes, mesh_volume=a.mesh_volume)
