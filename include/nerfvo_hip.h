@@ -1274,6 +1274,61 @@ typedef struct nvo_tsdf_blocks_iso_args {
 int nvo_tsdf_blocks_iso_count(nvo_stream_t stream, const nvo_tsdf_blocks_iso_args* args);
 int nvo_tsdf_blocks_iso_emit(nvo_stream_t stream, const nvo_tsdf_blocks_iso_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * N. 2-D evaluation metrics of batches of frames (csrc/metrics2d.hip): the accumulators behind the reference's
+ *    metrics_2d_*.csv -- PSNR, MSSIM and the eight depth errors -- for F frames per launch.  DESIGN.md section 16 states
+ *    the rules; tests/helpers/metrics2d_oracle.py restates the colour rule in numpy, operation for operation.  No float
+ *    atomics; every sum is either an integer or a float64 sum in an order fixed by (H, W), so a frame's row of a table
+ *    is bitwise the same on every run and whatever other frames share the launch.  Scratch is written before it is read.
+ *      nvo_m2d_color   table [F][3][NVO_M2D_COLOR_WORDS] int64, per frame and channel:
+ *                        [0] sum of uint8(uint8(a - b) * uint8(a - b)), both operations mod 256 (uint8 form, else 0)
+ *                        [1] sum of (a - b)^2 (uint8 form, else 0)
+ *                        [2] sum over the pixels of llrint(double(s) * 2^32), s the fp32 SSIM map:
+ *                            x = (float(u) / 255) * 2 - 1 (uint8 form); planes a, b, a*a, b*b, a*b; 11-tap window `taps`
+ *                            along the row, then along the column, each acc = acc + taps[t] * v from 0, t ascending, the
+ *                            image zero outside; maa = ma*ma, mbb = mb*mb, mab = ma*mb, va = saa - maa, vb = sbb - mbb,
+ *                            cab = sab - mab, s = ((2 mab + C1) * (2 cab + C2)) / (((maa + mbb) + C1) * ((va + vb) + C2)),
+ *                            C1 = 0.0001f, C2 = 0.0009f.  One workgroup per NVO_M2D_TILE_H x NVO_M2D_TILE_W tile and channel.
+ *                      uint8 form: a, b [F][H][W][3]; float form: a, b [F][3][H][W] float32.  3 H W < 2^30, 3 F <= 65535.
+ *      nvo_m2d_depth   table [F][NVO_M2D_DEPTH_WORDS] 8-byte words per frame, over the pixels with
+ *                      gt > 0 && pred > 0 && gt < 5 && pred < 5 (float64 whatever comes in):
+ *                        [0..4] float64 sums of diff / p, diff, diff^2 / p, diff^2, (log p - log gt)^2 with
+ *                               p = pred * scale, scale = (sum gt / n) / (sum pred / n) or 1, diff = |p - gt|
+ *                        [5] int64 n; [6..8] int64 counts of max(gt / p, p / gt) < 1.25, 1.25^2, 1.25^3
+ *                      A frame is cut into nvo_m2d_depth_chunks(H, W) contiguous chunks, a workgroup per chunk: a thread
+ *                      sums its pixels (stride 256) in ascending order, the 256 threads fold as a binary tree
+ *                      (v[t] += v[t + s] for t < s, s = 128 .. 1), the chunks are added in ascending order.  H W < 2^31, F <= 65535.
+ * ---------------------------------------------------------------------------------------------- */
+#define NVO_M2D_TILE_H 32
+#define NVO_M2D_TILE_W 32
+#define NVO_M2D_TAPS 11
+#define NVO_M2D_COLOR_WORDS 3
+#define NVO_M2D_DEPTH_WORDS 9
+typedef struct nvo_m2d_color_args {
+    const void* a;               /* uint8 [F][H][W][3] or float [F][3][H][W] */
+    const void* b;
+    int64_t* table;              /* [F][3][NVO_M2D_COLOR_WORDS] */
+    void* scratch;               /* nvo_m2d_color_scratch_bytes(F, H, W), 8-byte aligned */
+    uint32_t F, H, W;
+    int32_t is_float;
+    float taps[NVO_M2D_TAPS];
+} nvo_m2d_color_args;
+uint64_t nvo_m2d_color_scratch_bytes(uint32_t F, uint32_t H, uint32_t W);
+int nvo_m2d_color(nvo_stream_t stream, const nvo_m2d_color_args* args);
+
+typedef struct nvo_m2d_depth_args {
+    const void* gt;              /* [F][H][W] float32 or float64 */
+    const void* pred;
+    void* table;                 /* [F][NVO_M2D_DEPTH_WORDS] 8-byte words */
+    void* scratch;               /* nvo_m2d_depth_scratch_bytes(F, H, W), 8-byte aligned */
+    uint32_t F, H, W;
+    int32_t gt_f64, pred_f64;    /* 1: float64 input */
+    int32_t with_scale;
+} nvo_m2d_depth_args;
+uint32_t nvo_m2d_depth_chunks(uint32_t H, uint32_t W);
+uint64_t nvo_m2d_depth_scratch_bytes(uint32_t F, uint32_t H, uint32_t W);
+int nvo_m2d_depth(nvo_stream_t stream, const nvo_m2d_depth_args* args);
+
 #ifdef __cplusplus
 }
 #endif

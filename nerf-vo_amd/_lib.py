@@ -245,6 +245,25 @@ TSDF_BLOCKS_MAX_TABLE = 1 << 26         # NVO_TSDF_BLOCKS_MAX_TABLE
 TSDF_BLOCKS_MAX_ALLOCATED = 1 << 22     # NVO_TSDF_BLOCKS_MAX_ALLOCATED
 
 
+class M2dColorArgs(C.Structure):
+    """mirror of nvo_m2d_color_args"""
+    _fields_ = [("a", _p), ("b", _p), ("table", _p), ("scratch", _p), ("F", _u32), ("H", _u32), ("W", _u32), ("is_float", _i32),
+                ("taps", _f * 11)]
+
+
+class M2dDepthArgs(C.Structure):
+    """mirror of nvo_m2d_depth_args"""
+    _fields_ = [("gt", _p), ("pred", _p), ("table", _p), ("scratch", _p), ("F", _u32), ("H", _u32), ("W", _u32),
+                ("gt_f64", _i32), ("pred_f64", _i32), ("with_scale", _i32)]
+
+
+M2D_TILE_H = 32        # NVO_M2D_TILE_H
+M2D_TILE_W = 32        # NVO_M2D_TILE_W
+M2D_TAPS = 11          # NVO_M2D_TAPS
+M2D_COLOR_WORDS = 3    # NVO_M2D_COLOR_WORDS
+M2D_DEPTH_WORDS = 9    # NVO_M2D_DEPTH_WORDS
+
+
 _SIGNATURES = {
     "nvo_last_error": (C.c_char_p, []),
     "nvo_version": (_int, []),
@@ -352,6 +371,12 @@ _SIGNATURES = {
     "nvo_tsdf_blocks_integrate": (_int, [_p, C.POINTER(TsdfBlocksArgs)]),
     "nvo_tsdf_blocks_iso_count": (_int, [_p, C.POINTER(TsdfBlocksIsoArgs)]),
     "nvo_tsdf_blocks_iso_emit": (_int, [_p, C.POINTER(TsdfBlocksIsoArgs)]),
+    # group N
+    "nvo_m2d_color_scratch_bytes": (_u64, [_u32, _u32, _u32]),
+    "nvo_m2d_color": (_int, [_p, C.POINTER(M2dColorArgs)]),
+    "nvo_m2d_depth_chunks": (_u32, [_u32, _u32]),
+    "nvo_m2d_depth_scratch_bytes": (_u64, [_u32, _u32, _u32]),
+    "nvo_m2d_depth": (_int, [_p, C.POINTER(M2dDepthArgs)]),
     # group E
     "nvo_adam_step": (_int, [_p, C.POINTER(AdamArgs), _u32, C.POINTER(AdamGroup), C.POINTER(AdamTail)]),
     "nvo_opt_commit": (_int, [_p, C.POINTER(OptCommitArgs), C.POINTER(StepScalars)]),

@@ -27,6 +27,11 @@ followed by Open3D's Poisson reconstruction, ``EvaluationRenderer.render_point_c
 reconstructs the mesh from the same cloud (poisson.py: the project's dense-lattice Poisson rule, csrc/poisson.hip; parity with
 Open3D's octree solver unpinned).
 
+The 2-D table can also be computed on the GPU, on batches of frames (``Evaluator2D(device=...)``, metrics2d.py,
+csrc/metrics2d.hip); the host functions below stay the default.  The trajectory table (``metrics_trajectory.csv``,
+evaluator.py:55-83) is ``EvaluatorTrajectory`` over ``kabsch_umeyama_alignment`` / ``calculate_absolute_trajectory_error``
+(evaluation_utils.py:230-286), float64 on the host, pinned by tests/golden/make_golden_trajectory.py.
+
 The numeric functions are pinned by the reference's own outputs: tests/golden/make_golden_evaluation.py and
 make_golden_metrics3d.py execute the reference's definitions on seeded inputs and tests/test_evaluation_cpu.py /
 test_metrics3d_cpu.py compare.  For the 3-D table that covers the five formulae and the nearest-neighbour distances;
@@ -108,6 +113,44 @@ def calculate_depth_metrics_2d(frame_depth_gt: np.ndarray, frame_depth_pred: np.
         "delta2": np.mean((ratio < 1.25 ** 2).astype("float")),
         "delta3": np.mean((ratio < 1.25 ** 3).astype("float")),
     }
+
+
+ATE_METRICS = ("absolute_trajectory_error_rmse", "absolute_trajectory_error_mean", "absolute_trajectory_error_median",
+               "absolute_trajectory_error_std", "absolute_trajectory_error_max", "absolute_trajectory_error_min")
+
+
+def kabsch_umeyama_alignment(points_target: np.ndarray, points_source: np.ndarray, with_scale: bool = True) -> tuple:
+    """Least-squares similarity ``target ~ scale * rotation @ source + translation`` of two [N, D] point sets (Umeyama 1991;
+    evaluation_utils.py:230-252): SVD of the cross-covariance, the last singular direction flipped when the two bases
+    disagree in handedness (a reflection is never returned), scale = target variance over the signed singular-value sum.
+    Returns ``(rotation [D, D], translation [D, 1], scale)``; float64 on the host."""
+    points_target, points_source = np.asarray(points_target), np.asarray(points_source)
+    assert points_target.shape == points_source.shape
+    n, dims = points_target.shape
+    mean_target, mean_source = points_target.mean(axis=0), points_source.mean(axis=0)
+    variance_target = np.mean(np.linalg.norm(points_target - mean_target, axis=1) ** 2)
+    covariance = ((points_target - mean_target).T @ (points_source - mean_source)) / n
+    u, d, vt = np.linalg.svd(covariance)
+    s = np.diag([1] * (dims - 1) + [np.sign(np.linalg.det(u) * np.linalg.det(vt))])
+    rotation = u @ s @ vt
+    scale = variance_target / np.trace(np.diag(d) @ s) if with_scale else 1.0
+    translation = mean_target - scale * rotation @ mean_source
+    return rotation, translation.reshape(dims, 1), scale
+
+
+def calculate_absolute_trajectory_error(matrices_origin2frame_gt: np.ndarray, matrices_origin2frame_pred: np.ndarray,
+                                        with_scale: bool = True) -> dict:
+    """The six absolute-trajectory-error statistics of the predicted camera centres after their Kabsch-Umeyama alignment
+    onto the ground truth's (evaluation_utils.py:255-286).  [N, 4, 4] camera-to-world matrices each."""
+    trajectory_gt = np.asarray(matrices_origin2frame_gt)[:, :3, 3]
+    trajectory_pred = np.asarray(matrices_origin2frame_pred)[:, :3, 3]
+    rotation, translation, scale = kabsch_umeyama_alignment(trajectory_gt, trajectory_pred, with_scale=with_scale)
+    aligned = (scale * rotation @ trajectory_pred.T + translation).T
+    residual = aligned - trajectory_gt
+    error = np.sqrt(np.sum(np.multiply(residual, residual), axis=1))
+    values = (np.sqrt(np.dot(error, error) / len(error)), np.mean(error), np.median(error), np.std(error), np.max(error),
+              np.min(error))
+    return dict(zip(ATE_METRICS, values))
 
 
 def calculate_mssim(image1: torch.Tensor, image2: torch.Tensor) -> float:
@@ -358,12 +401,54 @@ class Evaluator2D:
     """Per-frame depth + colour metrics of the frames ``EvaluationRenderer.render_frames`` wrote
     (evaluator.py:88-146): ``metrics_2d_<folder>.csv`` (one row per frame) and ``.json`` (column means)."""
 
-    def __init__(self, dataset, keyframes, dir_prediction: str, dir_result: str, lpips_loss=None) -> None:
+    def __init__(self, dataset, keyframes, dir_prediction: str, dir_result: str, lpips_loss=None, device=None,
+                 frames_per_launch: int = 8) -> None:
+        """``device``: None computes every frame on the host (the functions above); a CUDA device uploads the decoded
+        frames ``frames_per_launch`` at a time and computes the same columns there (metrics2d.py, csrc/metrics2d.hip):
+        ``psnr`` is equal, the others agree to the bounds of DESIGN.md section 16.  ``lpips_loss`` stays on the host."""
         self.dataset = dataset
         self.keyframes = list(keyframes)
         self.dir_prediction = dir_prediction
         self.dir_result = dir_result
         self.lpips_loss = lpips_loss
+        self.device = None if device is None else torch.device(device)
+        self.frames_per_launch = max(int(frames_per_launch), 1)
+        if self.device is not None and self.device.type != "cuda":
+            raise ValueError(f"Evaluator2D: device must be None (host) or a CUDA device, got {device!r}")
+
+    def _rows_on_device(self, depths_gt, depths_pred, colors_gt, colors_pred) -> list:
+        from . import metrics2d
+
+        def depth_array(d):  # (the kernel takes float32 and float64 and computes in float64 either way)
+            d = np.asarray(d)
+            return d if d.dtype in (np.float32, np.float64) else d.astype(np.float64)
+
+        def key(frame):  # a launch takes frames of one shape and type
+            return tuple((x.shape, x.dtype) for x in frame)
+
+        def upload(arrays):
+            return torch.from_numpy(np.stack(arrays)).to(self.device)
+
+        def to_tensor(img):
+            return torch.from_numpy(np.ascontiguousarray(img.transpose(2, 0, 1))).unsqueeze(0).float().div(255.0) * 2 - 1
+
+        frames = [(depth_array(dg), depth_array(dp), np.asarray(cg), np.asarray(cp))
+                  for dg, dp, cg, cp in zip(depths_gt, depths_pred, colors_gt, colors_pred)]
+        rows, lo = [], 0
+        while lo < len(frames):
+            hi = lo + 1
+            while hi < len(frames) and hi - lo < self.frames_per_launch and key(frames[hi]) == key(frames[lo]):
+                hi += 1
+            d_gt, d_pred, c_gt, c_pred = (list(column) for column in zip(*frames[lo:hi]))
+            depth_rows = metrics2d.depth_metrics(upload(d_gt), upload(d_pred))
+            color_rows = metrics2d.color_metrics(upload(c_gt), upload(c_pred))
+            for k, (depth_row, color_row) in enumerate(zip(depth_rows, color_rows)):
+                row = {**depth_row, **color_row}
+                if self.lpips_loss is not None:  # on the host, fed as calculate_color_metrics_2d feeds it
+                    row["lpips"] = float(self.lpips_loss(to_tensor(c_gt[k]) * 2 - 1, to_tensor(c_pred[k]) * 2 - 1))
+                rows.append(row)
+            lo = hi
+        return rows
 
     def calculate_metrics_2d(self, mode: str = "evaluation_frames") -> dict:
         import pandas as pd
@@ -376,11 +461,14 @@ class Evaluator2D:
         depths_pred = [read_depth_png16(os.path.join(depth_dir, f)) / self.dataset.camera_intrinsics["depth_scale"]
                        for f in sorted(os.listdir(depth_dir)) if f.endswith(".png")]
         rows = []
-        for d_gt, d_pred, c_gt, c_pred in zip(depths_gt, depths_pred, colors_gt, colors_pred):
-            row = dict(calculate_depth_metrics_2d(frame_depth_gt=d_gt, frame_depth_pred=d_pred))
-            row.update(calculate_color_metrics_2d(frame_color_gt=c_gt, frame_color_pred=c_pred,
-                                                  lpips_loss=self.lpips_loss))
-            rows.append(row)
+        if self.device is not None:
+            rows = self._rows_on_device(depths_gt, depths_pred, colors_gt, colors_pred)
+        else:
+            for d_gt, d_pred, c_gt, c_pred in zip(depths_gt, depths_pred, colors_gt, colors_pred):
+                row = dict(calculate_depth_metrics_2d(frame_depth_gt=d_gt, frame_depth_pred=d_pred))
+                row.update(calculate_color_metrics_2d(frame_color_gt=c_gt, frame_color_pred=c_pred,
+                                                      lpips_loss=self.lpips_loss))
+                rows.append(row)
         table = pd.DataFrame(rows)
         os.makedirs(self.dir_result, exist_ok=True)
         table.to_csv(f"{self.dir_result}/metrics_2d_{folder}.csv", index=False)
@@ -388,6 +476,49 @@ class Evaluator2D:
         with open(f"{self.dir_result}/metrics_2d_{folder}.json", "w") as file:
             json.dump(means, file)
         return means
+
+
+class EvaluatorTrajectory:
+    """``Evaluator.calculate_metrics_trajectory`` (evaluator.py:55-83): the keyframe trajectories under
+    ``<dir_prediction>/matrices/matrices_origin2frame_keyframes_{tracking,mapping}.json`` against the ground-truth poses
+    of the keyframes, aligned with scale -> ``<dir_result>/metrics_trajectory.csv``, one row per file: the six ATE
+    statistics and ``trajectory``.  The reference reads both files; tracking is not part of this project, so a file that
+    is absent is left out, and only the absence of both is an error.  ``EvaluationRenderer.export_keyframe_poses``
+    writes the mapping file."""
+
+    TRAJECTORIES = ("keyframes_tracking", "keyframes_mapping")
+
+    def __init__(self, dataset, keyframes, dir_prediction: str, dir_result: str) -> None:
+        self.dataset = dataset
+        self.keyframes = list(keyframes)
+        self.dir_prediction = dir_prediction
+        self.dir_result = dir_result
+
+    def calculate_metrics_trajectory(self) -> dict:
+        import pandas as pd
+
+        poses_gt = np.stack([np.asarray(self.dataset.camera_extrinsics[i], dtype=np.float64) for i in self.keyframes])
+        rows = []
+        for trajectory in self.TRAJECTORIES:
+            path = f"{self.dir_prediction}/matrices/matrices_origin2frame_{trajectory}.json"
+            if not os.path.exists(path):
+                continue
+            with open(path) as file:
+                poses_pred = np.array(json.load(file))
+            if poses_pred.shape != poses_gt.shape:
+                raise ValueError(f"{path} holds poses of shape {poses_pred.shape}, the {len(self.keyframes)} keyframes need "
+                                 f"{poses_gt.shape}")
+            row = calculate_absolute_trajectory_error(poses_gt, poses_pred, with_scale=True)
+            row["trajectory"] = trajectory
+            rows.append(row)
+        if not rows:
+            raise FileNotFoundError(f"{self.dir_prediction}/matrices holds neither matrices_origin2frame_keyframes_tracking.json "
+                                    "nor matrices_origin2frame_keyframes_mapping.json (EvaluationRenderer.export_keyframe_poses "
+                                    "writes the latter)")
+        table = pd.DataFrame(rows, columns=list(ATE_METRICS) + ["trajectory"])
+        os.makedirs(self.dir_result, exist_ok=True)
+        table.to_csv(f"{self.dir_result}/metrics_trajectory.csv", index=False)
+        return table[list(ATE_METRICS)].squeeze().to_dict()
 
 
 def rotate_normals(normals, matrix, scale: float) -> torch.Tensor:

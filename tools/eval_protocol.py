@@ -124,8 +124,12 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
         camera_optimizer_mode=None, pose_noise=None, deterministic=False, seed=42, dynamic_loss_scale=None, out_dir=None,
         quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None, mesh=False, metrics_3d=False,
         mesh_nerf=False, pointcloud=False, pointcloud_points=33554432, poisson_depth=None, mesh_nerf_points=None,
-        mesh_nerf_attributes=False, mesh_volume="dense"):
-    """``mesh_volume``: the volume ``render_mesh(source='frames')`` fuses into, 'dense' or 'blocks' (nerf_vo_amd/tsdf.py).
+        mesh_nerf_attributes=False, mesh_volume="dense", metrics_device="cpu"):
+    """``metrics_device``: 'cpu' computes metrics_2d_*.csv on the host, 'cuda' on the GPU (``Evaluator2D(device=...)``,
+    nerf_vo_amd/metrics2d.py).  The trajectory table results/metrics_trajectory.csv (run.py:78) is always written: its
+    ``keyframes_mapping`` row scores the exported (optimised) keyframe poses, its ``keyframes_tracking`` row the poses as
+    ingested, written with the same translation scaling -- the place the reference's tracker output takes.
+    ``mesh_volume``: the volume ``render_mesh(source='frames')`` fuses into, 'dense' or 'blocks' (nerf_vo_amd/tsdf.py).
     ``method``: 'nerfstudio' (the default mapper) or 'instant-ngp' (the occupancy-grid back-end through the pyngp facade,
     /root/reference/nerf_vo/mapping/instant_ngp.py + evaluation/nerf_renderer.py:221-320; the room is shrunk by
     ``scene_scale``, default 0.5, so that it lies inside that back-end's scene box: it takes poses as they come).
@@ -137,7 +141,11 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
     ``pointcloud`` (both back-ends): also ``render_point_cloud(num_points=pointcloud_points)`` -- the oriented, coloured cloud
     of the field, outliers removed, cropped to the ground-truth mesh's box -- and its score, results/metrics_3d_pointcloud.csv."""
     entry.build()
-    from nerf_vo_amd.evaluation import (EvaluationRenderer, Evaluator2D, Evaluator3D, read_color, transform_matrices_pred2gt)
+    from nerf_vo_amd.evaluation import (EvaluationRenderer, Evaluator2D, Evaluator3D, EvaluatorTrajectory, read_color,
+                                        transform_matrices_pred2gt)
+
+    if metrics_device not in ("cpu", "cuda"):
+        raise SystemExit(f"--metrics-device must be cpu or cuda, got {metrics_device!r}")
     from nerf_vo_amd.mapping.dataset import opencv_to_opengl
     from nerf_vo_amd.mapping.nerfstudio_mapper import Nerfstudio
     from nerf_vo_amd.mapping.renderer import NerfstudioRenderer, calculate_psnr_float
@@ -252,7 +260,18 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
                 "seconds_incl_ground_truth_mesh": seconds_3d}
         if "mesh_from_nerf" in table.index:
             m_3d["mesh_from_nerf"] = {k: float(v) for k, v in table.loc["mesh_from_nerf"].items()}
-    ev = Evaluator2D(ds, kf, args.dir_prediction, out_dir + "/results")
+    # run.py:78: results/metrics_trajectory.csv.  The mapping file is there (export_keyframe_poses); the tracking file holds
+    # the poses as ingested, translations scaled like the exported ones (the alignment's own scale absorbs the factor)
+    tracked = poses.double().numpy().copy()
+    tracked[:, :3, 3] *= renderer.pred2gt_transformation["scale_pred2gt"]
+    with open(f"{args.dir_prediction}/matrices/matrices_origin2frame_keyframes_tracking.json", "w") as file:
+        json.dump(tracked.tolist(), file)
+    EvaluatorTrajectory(ds, kf, args.dir_prediction, out_dir + "/results").calculate_metrics_trajectory()
+    import pandas as pd
+
+    m_traj = {row["trajectory"]: {k: float(v) for k, v in row.items() if k != "trajectory"}
+              for row in pd.read_csv(out_dir + "/results/metrics_trajectory.csv").to_dict("records")}
+    ev = Evaluator2D(ds, kf, args.dir_prediction, out_dir + "/results", device=None if metrics_device == "cpu" else dev)
     m_eval = ev.calculate_metrics_2d(mode="evaluation_frames")
     m_kf = {}
     if keyframe_views:  # (every keyframe through JPEG / PNG files and the CPU metrics: seconds per hundred frames)
@@ -280,6 +299,8 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
            "pose_error_after_frame0_alignment": pose_err, "pose_error_of_ingested_poses": _pose_errors(ing, gt_kf),
            # the same error split into the cameras' common rigid motion (gauge) and the residual
            "pose_error_gauge_split": _gauge_split(traj, gt_kf),
+           # results/metrics_trajectory.csv: Kabsch-Umeyama alignment with scale, the reference's six ATE statistics
+           "metrics_trajectory": m_traj, "metrics_device": metrics_device,
            "pose_adjustment_rms": float((eng.pose_adjustment if ngp else eng.view("camera_opt.pose_adjustment")).pow(2).mean().sqrt()),
            "deterministic": bool(deterministic), "seed": seed, "exported_poses": int(exported.shape[0])}
     if mesh_info is not None:
@@ -336,10 +357,13 @@ if __name__ == "__main__":
                     "cropped to the ground-truth mesh's box (pointcloud/pointcloud_from_nerf.ply), and score it "
                     "(results/metrics_3d_pointcloud.csv)")
     ap.add_argument("--pointcloud-points", type=int, default=33554432, help="points of the cloud before outlier removal and crop")
+    ap.add_argument("--metrics-device", default="cpu", choices=["cpu", "cuda"], help="where metrics_2d_*.csv is computed: the host "
+                    "functions, or the HIP kernels of nerf_vo_amd/metrics2d.py on batches of uploaded frames")
     a = ap.parse_args()
     run(a.keyframes, a.height, a.width, a.iterations, eval_frames=a.eval_frames, camera_optimizer_mode=a.camera_optimizer_mode,
         pose_noise=a.pose_noise, deterministic=a.deterministic, seed=a.seed, quiet=False,
         dynamic_loss_scale=False if a.static_loss_scale else None, keyframe_views=not a.no_keyframe_views,
         method=a.method, scene_scale=a.scene_scale, mesh=a.mesh, metrics_3d=a.metrics_3d, mesh_nerf=a.mesh_nerf,
         pointcloud=a.pointcloud, pointcloud_points=a.pointcloud_points, poisson_depth=a.poisson_depth,
-        mesh_nerf_points=a.mesh_nerf_points, mesh_nerf_attributes=a.mesh_nerf_attributes, mesh_volume=a.mesh_volume)
+        mesh_nerf_points=a.mesh_nerf_points, mesh_nerf_attributes=a.mesh_nerf_attributes, mesh_volume=a.mesh_volume,
+        metrics_device=a.metrics_device)
