@@ -9,7 +9,7 @@
 //   vertex order: ascending (linear index of a, kind)
 //   position:     t = clamp((threshold - va) / (vb - va), 0, 1); g = float(a_axis) + (d_axis ? t : 0);
 //                 out = lower_axis + g * step_axis                      (fp32 as written, -ffp-contract=off)
-//   faces:        active cubes ascending, tetrahedra 0..5, the triangles of kIsoTriEdge[tet][case] (winding applied)
+//   faces:        active cubes ascending, tetrahedra 0..5, the triangles of kIsoTriEdge at (tet, case), winding applied
 //
 // Structure: a workgroup owns `points_per_workgroup` CONSECUTIVE lattice points and walks them 256 at a time, so ranks
 // inside a workgroup follow the rule's order.
@@ -21,10 +21,7 @@
 // The 8 samples a point reads are its cube's 8 corners and at the same time the far ends of its 7 edge kinds.
 #include "nvo_kernels.h"
 #include "../../include/nerfvo_hip.h"
-#include "iso_tables.h"
 #include "iso_dev.h"
-
-#include <math.h>
 
 namespace {
 
@@ -106,29 +103,7 @@ __global__ void __launch_bounds__(kBlock) k_iso_count(const nvo_iso_args a, uint
             const uint32_t bits = corner_bits(a, p, i, j, k);
             const uint32_t in = bits & 0xFFu, have = bits >> 8;
             const uint32_t differ = ((bits & 1u) ? ~in : in) & have & 0xFEu;  // corners on the other side than the point
-            if (differ != 0u) {
-                const uint32_t nb = neighbourhood(a, i, j, k);
-#pragma unroll
-                for (uint32_t kind = 0; kind < 7; ++kind) {
-                    if (!((differ >> kIsoKindCorner[kind]) & 1u)) continue;
-                    const uint32_t dx = kIsoKind[kind][0], dy = kIsoKind[kind][1], dz = kIsoKind[kind][2];
-                    // cubes with both ends among their corners: minimum corner = point - o, o = 0 on the edge's axes
-                    bool any = false;
-                    for (uint32_t ox = 0; ox <= 1u - dx; ++ox)
-                        for (uint32_t oy = 0; oy <= 1u - dy; ++oy)
-                            for (uint32_t oz = 0; oz <= 1u - dz; ++oz) any = any || cube_active(nb, ox, oy, oz);
-                    mask |= (any ? 1u : 0u) << kind;
-                }
-                if (cube_active(nb, 0, 0, 0)) {
-#pragma unroll
-                    for (uint32_t t = 0; t < 6; ++t) {
-                        uint32_t c = 0;
-#pragma unroll
-                        for (uint32_t m = 0; m < 4; ++m) c |= ((in >> kIsoTet[t][m]) & 1u) << m;
-                        tris += kIsoTriCount[t][c];
-                    }
-                }
-            }
+            if (differ != 0u) iso_classify(in, differ, neighbourhood(a, i, j, k), mask, tris);
         }
         uint32_t vtot, ttot;
         const uint32_t vex = block_excl_scan(__popc(mask), lds, vtot);
@@ -173,14 +148,12 @@ __global__ void __launch_bounds__(kBlock) k_iso_emit(const nvo_iso_args a, uint3
                 if (!((mask >> kind) & 1u)) continue;
                 const uint32_t dx = kIsoKind[kind][0], dy = kIsoKind[kind][1], dz = kIsoKind[kind][2];
                 const float vb = a.values[(size_t)p + ((size_t)dx * a.ny + dy) * a.nz + dz];
-                float t = (a.threshold - va) / (vb - va);
-                t = fminf(fmaxf(t, 0.f), 1.f);
-                const float gx = (float)i + (dx ? t : 0.f), gy = (float)j + (dy ? t : 0.f), gz = (float)k + (dz ? t : 0.f);
+                const float3 pos = iso_vertex(i, j, k, dx, dy, dz, iso_cut(va, vb, a.threshold), a.lower, a.step);
                 if (id < a.n_vertices) {  // (always, when vertex_base is the prefix sum of this scratch's totals)
                     float* o = a.vertices + (size_t)id * 3;
-                    o[0] = a.lower[0] + gx * a.step[0];
-                    o[1] = a.lower[1] + gy * a.step[1];
-                    o[2] = a.lower[2] + gz * a.step[2];
+                    o[0] = pos.x;
+                    o[1] = pos.y;
+                    o[2] = pos.z;
                 }
                 ++id;
             }
@@ -194,31 +167,11 @@ __global__ void __launch_bounds__(kBlock) k_iso_emit(const nvo_iso_args a, uint3
                 const size_t q = (size_t)p + ((size_t)kIsoCorner[m][0] * a.ny + kIsoCorner[m][1]) * a.nz + kIsoCorner[m][2];
                 in |= (a.values[q] > a.threshold ? 1u : 0u) << m;
             }
-            uint64_t f = fbase + trun + tex;
-            for (uint32_t t = 0; t < 6; ++t) {
-                uint32_t c = 0;
-#pragma unroll
-                for (uint32_t m = 0; m < 4; ++m) c |= ((in >> kIsoTet[t][m]) & 1u) << m;
-                const uint32_t nt = kIsoTriCount[t][c];
-                for (uint32_t r = 0; r < nt; ++r) {
-                    int32_t ids[3];
-#pragma unroll
-                    for (uint32_t v = 0; v < 3; ++v) {
-                        const uint32_t e = kIsoTriEdge[t][c][3 * r + v];
-                        const uint32_t oc = (e >> 3) & 7u, kind = e & 7u;
-                        const uint32_t q = p + (kIsoCorner[oc][0] * a.ny + kIsoCorner[oc][1]) * a.nz + kIsoCorner[oc][2];  // < n
-                        const uint32_t below = (uint32_t)s.mask[q] & ((1u << kind) - 1u);
-                        ids[v] = (int32_t)((uint64_t)a.vertex_base[q / a.points_per_workgroup] + s.vrank[q] + __popc(below));
-                    }
-                    if (f < a.n_faces) {
-                        int32_t* o = a.faces + (size_t)f * 3;
-                        o[0] = ids[0];
-                        o[1] = ids[1];
-                        o[2] = ids[2];
-                    }
-                    ++f;
-                }
-            }
+            iso_emit_faces(in, fbase + trun + tex, a.n_faces, a.faces, [&] __device__(uint32_t oc, uint32_t kind) {
+                const uint32_t q = p + (kIsoCorner[oc][0] * a.ny + kIsoCorner[oc][1]) * a.nz + kIsoCorner[oc][2];  // < n
+                const uint32_t below = (uint32_t)s.mask[q] & ((1u << kind) - 1u);
+                return (int32_t)((uint64_t)a.vertex_base[q / a.points_per_workgroup] + s.vrank[q] + __popc(below));
+            });
         }
         trun += ttot;
     }
@@ -283,10 +236,7 @@ int nvo_iso_emit(nvo_stream_t stream, const nvo_iso_args* args) {
     const nvo_iso_args a = *args;
     uint64_t n, groups;
     if (int rc = iso_check(a, "iso_emit", &n, &groups)) return rc;
-    NVO_REQUIRE(a.n_vertices < (1ull << 31) && a.n_faces < (1ull << 31),
-                "iso_emit: %llu vertices and %llu faces: each must stay below 2^31 (int32 face indices) -- extract a smaller box or "
-                "a coarser lattice",
-                (unsigned long long)a.n_vertices, (unsigned long long)a.n_faces);
+    if (int rc = iso_counts_check("iso_emit", a.n_vertices, a.n_faces)) return rc;
     if (a.n_vertices == 0 && a.n_faces == 0) return NVO_OK;
     NVO_REQUIRE(a.vertex_base && a.face_base && (a.vertices || a.n_vertices == 0) && (a.faces || a.n_faces == 0),
                 "iso_emit: NULL vertex_base, face_base, vertices or faces");

@@ -1,7 +1,8 @@
 // Iso-surface of the block-sparse TSDF volume (include/nerfvo_hip.h section M; DESIGN.md "Block-sparse TSDF volume"): the
-// edge-owned marching tetrahedra of iso.hip -- same ownership, case table, winding and position formula -- on the lattice
-// [8 tbx][8 tby][8 tbz] read through the block table.  values = -tsdf, threshold 0, a sample is valid when its block is
-// allocated and its weight reaches the threshold; a sample of an unallocated block is invalid.
+// edge-owned marching tetrahedra of iso.hip -- the per-point rules of iso_dev.h that iso.hip calls: ownership, case table,
+// winding and position formula exist once, there -- on the lattice [8 tbx][8 tby][8 tbz] read through the block table.
+// values = -tsdf, threshold 0, a sample is valid when its block is allocated and its weight reaches the threshold; a
+// sample of an unallocated block is invalid.
 //
 // A workgroup owns one block of `order` (table indices, ascending) and walks its 512 points in local order, 256 at a
 // time, so ranks inside a workgroup follow the rule's order.  It first stages the block with a halo of one sample on
@@ -11,10 +12,8 @@
 // by block ID, so a triangle finds a vertex owned by a point of a neighbouring block without a second table.
 #include "nvo_kernels.h"
 #include "../../include/nerfvo_hip.h"
-#include "iso_tables.h"
 #include "iso_dev.h"
-
-#include <math.h>
+#include "tsdf_dev.h"
 
 namespace {
 
@@ -115,26 +114,7 @@ __global__ void __launch_bounds__(kBlock) k_tsdf_blocks_iso_count(const nvo_tsdf
 #pragma unroll
                     for (uint32_t dz = 0; dz < 3; ++dz)
                         nb |= (uint32_t)h.ok[hc + (dx * kH + dy) * kH + dz - (kH * kH + kH + 1u)] << (dx * 9u + dy * 3u + dz);
-#pragma unroll
-            for (uint32_t kind = 0; kind < 7; ++kind) {
-                if (!((differ >> kIsoKindCorner[kind]) & 1u)) continue;
-                const uint32_t dx = kIsoKind[kind][0], dy = kIsoKind[kind][1], dz = kIsoKind[kind][2];
-                // cubes with both ends among their corners: minimum corner = point - o, o = 0 on the edge's axes
-                bool any = false;
-                for (uint32_t ox = 0; ox <= 1u - dx; ++ox)
-                    for (uint32_t oy = 0; oy <= 1u - dy; ++oy)
-                        for (uint32_t oz = 0; oz <= 1u - dz; ++oz) any = any || cube_active(nb, ox, oy, oz);
-                mask |= (any ? 1u : 0u) << kind;
-            }
-            if (cube_active(nb, 0, 0, 0)) {
-#pragma unroll
-                for (uint32_t t = 0; t < 6; ++t) {
-                    uint32_t c = 0;
-#pragma unroll
-                    for (uint32_t m = 0; m < 4; ++m) c |= ((in >> kIsoTet[t][m]) & 1u) << m;
-                    tris += kIsoTriCount[t][c];
-                }
-            }
+            iso_classify(in, differ, nb, mask, tris);
         }
         uint32_t vtot, ttot;
         const uint32_t vex = block_excl_scan(__popc(mask), lds, vtot);
@@ -159,6 +139,7 @@ __global__ void __launch_bounds__(kBlock) k_tsdf_blocks_iso_emit(const nvo_tsdf_
     if (!block_of(a, n_table, id, bi, bj, bk)) return;
     load_halo(a, bi, bj, bk, h);
     const uint64_t vbase = (uint64_t)a.vertex_base[id], fbase = (uint64_t)a.face_base[id];
+    const float step[3] = {a.voxel_size, a.voxel_size, a.voxel_size};
     uint32_t trun = 0;
     for (uint32_t round = 0; round < 2; ++round) {
         const uint32_t local = round * kBlock + threadIdx.x;
@@ -175,16 +156,15 @@ __global__ void __launch_bounds__(kBlock) k_tsdf_blocks_iso_emit(const nvo_tsdf_
                 if (!((mask >> kind) & 1u)) continue;
                 const uint32_t dx = kIsoKind[kind][0], dy = kIsoKind[kind][1], dz = kIsoKind[kind][2];
                 const float vb = h.val[hc + (dx * kH + dy) * kH + dz];
-                float t = (0.f - va) / (vb - va);
-                t = fminf(fmaxf(t, 0.f), 1.f);
-                const float gx = (float)i + (dx ? t : 0.f), gy = (float)j + (dy ? t : 0.f), gz = (float)k + (dz ? t : 0.f);
+                const float t = iso_cut(va, vb, 0.f);
+                const float3 pos = iso_vertex(i, j, k, dx, dy, dz, t, a.lower, step);
                 uint32_t lb;
                 const int32_t idb = far_point(h, li, lj, lk, dx, dy, dz, lb);  // allocated: the edge lies in an active cube
                 if (vid < a.n_vertices && idb >= 0) {  // (always, when vertex_base is the prefix sum of this count's totals)
                     float* o = a.vertices + (size_t)vid * 3;
-                    o[0] = a.lower[0] + gx * a.voxel_size;
-                    o[1] = a.lower[1] + gy * a.voxel_size;
-                    o[2] = a.lower[2] + gz * a.voxel_size;
+                    o[0] = pos.x;
+                    o[1] = pos.y;
+                    o[2] = pos.z;
                     const size_t cb = (size_t)idb * (3 * kBlockVoxels) + lb;
                     uint8_t* oc = a.colors + (size_t)vid * 3;
 #pragma unroll
@@ -203,54 +183,25 @@ __global__ void __launch_bounds__(kBlock) k_tsdf_blocks_iso_emit(const nvo_tsdf_
 #pragma unroll
             for (uint32_t m = 0; m < 8; ++m)
                 in |= (h.val[hc + (kIsoCorner[m][0] * kH + kIsoCorner[m][1]) * kH + kIsoCorner[m][2]] > 0.f ? 1u : 0u) << m;
-            uint64_t f = fbase + trun + tex;
-            for (uint32_t t = 0; t < 6; ++t) {
-                uint32_t c = 0;
-#pragma unroll
-                for (uint32_t m = 0; m < 4; ++m) c |= ((in >> kIsoTet[t][m]) & 1u) << m;
-                const uint32_t nt = kIsoTriCount[t][c];
-                for (uint32_t r = 0; r < nt; ++r) {
-                    int32_t ids[3];
-                    bool found = true;
-#pragma unroll
-                    for (uint32_t v = 0; v < 3; ++v) {
-                        const uint32_t e = kIsoTriEdge[t][c][3 * r + v];
-                        const uint32_t oc = (e >> 3) & 7u, kind = e & 7u;
-                        uint32_t lq;
-                        const int32_t idq = far_point(h, li, lj, lk, kIsoCorner[oc][0], kIsoCorner[oc][1], kIsoCorner[oc][2], lq);
-                        ids[v] = 0;
-                        if (idq < 0) {
-                            found = false;
-                            continue;
-                        }
-                        const size_t q = (size_t)idq * kBlockVoxels + lq;
-                        const uint32_t below = (uint32_t)a.mask[q] & ((1u << kind) - 1u);
-                        ids[v] = (int32_t)((uint64_t)a.vertex_base[idq] + a.vrank[q] + __popc(below));
-                    }
-                    if (f < a.n_faces && found) {
-                        int32_t* o = a.faces + (size_t)f * 3;
-                        o[0] = ids[0];
-                        o[1] = ids[1];
-                        o[2] = ids[2];
-                    }
-                    ++f;
-                }
-            }
+            iso_emit_faces(in, fbase + trun + tex, a.n_faces, a.faces, [&] __device__(uint32_t oc, uint32_t kind) {
+                uint32_t lq;
+                const int32_t idq = far_point(h, li, lj, lk, kIsoCorner[oc][0], kIsoCorner[oc][1], kIsoCorner[oc][2], lq);
+                if (idq < 0) return (int32_t)-1;  // a block that is not allocated
+                const size_t q = (size_t)idq * kBlockVoxels + lq;
+                const uint32_t below = (uint32_t)a.mask[q] & ((1u << kind) - 1u);
+                return (int32_t)((uint64_t)a.vertex_base[idq] + a.vrank[q] + __popc(below));
+            });
         }
         trun += ttot;
     }
 }
 
 int iso_blocks_check(const nvo_tsdf_blocks_iso_args& a, const char* what, uint64_t* n_table) {
-    NVO_REQUIRE(a.tbx >= 1 && a.tby >= 1 && a.tbz >= 1 && a.tbx <= NVO_TSDF_BLOCKS_MAX_TABLE && a.tby <= NVO_TSDF_BLOCKS_MAX_TABLE &&
-                    a.tbz <= NVO_TSDF_BLOCKS_MAX_TABLE && (uint64_t)a.tbx * a.tby <= NVO_TSDF_BLOCKS_MAX_TABLE &&
-                    (uint64_t)a.tbx * a.tby * a.tbz <= NVO_TSDF_BLOCKS_MAX_TABLE,
-                "%s: block table %u x %u x %u must have between 1 and 2^26 entries", what, a.tbx, a.tby, a.tbz);
+    if (int rc = tsdf_table_check(what, a.tbx, a.tby, a.tbz, n_table)) return rc;
     NVO_REQUIRE(a.n_allocated <= NVO_TSDF_BLOCKS_MAX_ALLOCATED && a.n_blocks <= a.n_allocated,
                 "%s: %u blocks to walk of %u allocated, of at most %u", what, a.n_blocks, a.n_allocated, NVO_TSDF_BLOCKS_MAX_ALLOCATED);
     NVO_REQUIRE(a.voxel_size > 0.f && a.voxel_size < INFINITY, "%s: voxel_size %g must be positive and finite", what,
                 (double)a.voxel_size);
-    *n_table = (uint64_t)a.tbx * a.tby * a.tbz;
     if (a.n_blocks == 0) return NVO_OK;
     NVO_REQUIRE(a.table && a.tsdf && a.weight && a.order && a.totals && a.vrank && a.mask && a.tcount, "%s: NULL argument", what);
     return NVO_OK;
@@ -277,9 +228,7 @@ int nvo_tsdf_blocks_iso_emit(nvo_stream_t stream, const nvo_tsdf_blocks_iso_args
     const nvo_tsdf_blocks_iso_args a = *args;
     uint64_t n_table;
     if (int rc = iso_blocks_check(a, "tsdf_blocks_iso_emit", &n_table)) return rc;
-    NVO_REQUIRE(a.n_vertices < (1ull << 31) && a.n_faces < (1ull << 31),
-                "tsdf_blocks_iso_emit: %llu vertices and %llu faces: each must stay below 2^31 (int32 face indices)",
-                (unsigned long long)a.n_vertices, (unsigned long long)a.n_faces);
+    if (int rc = iso_counts_check("tsdf_blocks_iso_emit", a.n_vertices, a.n_faces)) return rc;
     if (a.n_blocks == 0 || (a.n_vertices == 0 && a.n_faces == 0)) return NVO_OK;
     NVO_REQUIRE(a.color && a.vertex_base && a.face_base && (a.n_vertices == 0 || (a.vertices && a.colors)) && (a.faces || a.n_faces == 0),
                 "tsdf_blocks_iso_emit: NULL color, vertex_base, face_base, vertices, colors or faces");

@@ -1,14 +1,8 @@
 // TSDF fusion of depth + colour frames into a dense volume (DESIGN.md "TSDF fusion"): the integration step behind
 // EvaluationRenderer.render_mesh.  The reference fuses with Open3D's VoxelBlockGrid on the CPU; here the volume is a
-// dense box, one thread owns one voxel for the whole launch and applies the K frames of the launch in table order:
-//
-//   (xc,yc,zc) = R p + t                                  skip if zc <= 0
-//   u = fx*xc/zc + cx, v = fy*yc/zc + cy                  ui = floor(u + 0.5), vi = floor(v + 0.5); skip off-image
-//   d = depth[k][vi][ui]                                  skip unless 0 < d <= depth_max;  sdf = d - zc; skip if < -trunc
-//   s = min(sdf, trunc) / trunc                           tsdf = (w*tsdf + s)/(w+1), colour likewise, w += 1
-//
-// all in fp32 (the library is built with -ffp-contract=off).  The voxel's five values live in registers across the K
-// frames, are loaded when the first frame touches them and stored once: the result is bitwise independent of how a
+// dense box, one thread owns one voxel for the whole launch and applies the K frames of the launch in table order by
+// the per-voxel rule of tsdf_dev.h (tsdf_fuse_voxel, stated there).  The voxel's five values live in registers across the
+// K frames, are loaded when the first frame touches them and stored once: the result is bitwise independent of how a
 // frame sequence is cut into launches, and the volume is read and written at most once per launch.
 //
 // Work decomposition: a 256-thread workgroup owns a brick of 2 x 4 x 32 voxels (z fastest: every wave reads two runs
@@ -26,9 +20,7 @@
 // voxel_size: 0.04 pixel for fx = 600, coordinates of a few metres, voxel 1/64).  Bricks that straddle the camera plane
 // are never culled.
 #include "nvo_kernels.h"
-#include "../../include/nerfvo_hip.h"
-
-#include <math.h>
+#include "tsdf_dev.h"
 
 namespace {
 
@@ -100,47 +92,8 @@ k_tsdf_integrate(const nvo_tsdf_args a, uint32_t nby, uint32_t nbz, uint64_t n_b
             const float px = a.lower_x + (float)i * a.voxel_size;
             const float py = a.lower_y + (float)j * a.voxel_size;
             const float pz = a.lower_z + (float)k * a.voxel_size;
-            bool touched = false;
-            float t = 0.f, w = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
-            for (uint32_t f = 0; f < a.K; ++f) {
-                if (!((live >> f) & 1u)) continue;
-                const float* c = cam + 16 * f;
-                const float zc = c[8] * px + c[9] * py + c[10] * pz + c[11];
-                if (zc <= 0.f) continue;
-                const float xc = c[0] * px + c[1] * py + c[2] * pz + c[3];
-                const float yc = c[4] * px + c[5] * py + c[6] * pz + c[7];
-                const float u = c[12] * xc / zc + c[14], v = c[13] * yc / zc + c[15];
-                const float ui = floorf(u + 0.5f), vi = floorf(v + 0.5f);
-                if (!(ui >= 0.f && ui < fW && vi >= 0.f && vi < fH)) continue;  // a NaN fails
-                const size_t pix = ((size_t)f * a.H + (uint32_t)vi) * a.W + (uint32_t)ui;
-                const float d = a.depth[pix];
-                if (!(d > 0.f && d <= a.depth_max)) continue;  // a NaN fails
-                const float sdf = d - zc;
-                if (sdf < -a.trunc) continue;
-                if (!touched) {
-                    t = a.tsdf[idx];
-                    w = a.weight[idx];
-                    cr = a.color[idx];
-                    cg = a.color[n_vox + idx];
-                    cb = a.color[2 * n_vox + idx];
-                    touched = true;
-                }
-                const float s = fminf(sdf, a.trunc) / a.trunc;
-                const uint8_t* p = a.rgb + 3 * pix;
-                const float w1 = w + 1.f;
-                t = (w * t + s) / w1;
-                cr = (w * cr + (float)p[0]) / w1;
-                cg = (w * cg + (float)p[1]) / w1;
-                cb = (w * cb + (float)p[2]) / w1;
-                w = w1;
-            }
-            if (touched) {
-                a.tsdf[idx] = t;
-                a.weight[idx] = w;
-                a.color[idx] = cr;
-                a.color[n_vox + idx] = cg;
-                a.color[2 * n_vox + idx] = cb;
-            }
+            tsdf_fuse_voxel(cam, a.K, live, a.H, a.W, fW, fH, a.depth, a.rgb, a.trunc, a.depth_max, px, py, pz, a.tsdf,
+                            a.weight, a.color, idx, idx, n_vox);
         }
     }
 }
@@ -156,11 +109,7 @@ int nvo_tsdf_integrate(nvo_stream_t stream, const nvo_tsdf_args* args) {
     NVO_REQUIRE(a.nx >= 1 && a.ny >= 1 && a.nz >= 1 && a.nx < (1u << 31) && a.ny < (1u << 31) && a.nz < (1u << 31) &&
                     (uint64_t)a.nx * a.ny < (1ull << 31) && (uint64_t)a.nx * a.ny * a.nz < (1ull << 31),
                 "tsdf_integrate: volume %u x %u x %u must have between 1 and 2^31 - 1 voxels", a.nx, a.ny, a.nz);
-    NVO_REQUIRE(a.K >= 1 && a.K <= kMaxFrames, "tsdf_integrate: %u frames per launch not in 1..%u", a.K, kMaxFrames);
-    NVO_REQUIRE(a.H >= 1 && a.W >= 1 && a.H <= (1u << 16) && a.W <= (1u << 16), "tsdf_integrate: frame size %u x %u not in 1..65536",
-                a.W, a.H);
-    NVO_REQUIRE(a.voxel_size > 0.f && a.voxel_size < INFINITY && a.trunc > 0.f && a.trunc < INFINITY,
-                "tsdf_integrate: voxel_size %g and trunc %g must be positive and finite", (double)a.voxel_size, (double)a.trunc);
+    if (int rc = tsdf_frames_check("tsdf_integrate", a.K, a.H, a.W, a.voxel_size, a.trunc)) return rc;
     const uint32_t nbx = nvo_div_up(a.nx, kBX), nby = nvo_div_up(a.ny, kBY), nbz = nvo_div_up(a.nz, kBZ);
     const uint64_t n_bricks = (uint64_t)nbx * nby * nbz;
     const uint32_t grid = (uint32_t)(n_bricks < kMaxGrid ? n_bricks : kMaxGrid);

@@ -9,18 +9,15 @@
 //                            operation (the library is built with -ffp-contract=off; sqrtf and the divisions are correctly
 //                            rounded), and the sets are equal bit for bit.
 //   k_tsdf_blocks_integrate  a workgroup owns one listed block (512 voxels, two per thread, z fastest) and applies the
-//                            frames of the block's mask in table order by the per-voxel rule of k_tsdf_integrate,
-//                            expression for expression.  The five values of a voxel stay in registers across the frames
-//                            and are stored once, so the result is bitwise independent of how frames are cut into
-//                            launches.
+//                            frames of the block's mask in table order by the per-voxel rule of tsdf_dev.h
+//                            (tsdf_fuse_voxel: the function k_tsdf_integrate calls, here with the block's channel
+//                            stride), so the result is bitwise independent of how frames are cut into launches.
 //
 // Bounds: the launchers check the table's size, K, the frame size and the pointers; the kernels predicate every table
 // index, list entry and block id (an entry that fails is skipped), and a block index is compared as a float against the
 // table's extent BEFORE it is converted to an integer (a NaN or infinite world coordinate marks nothing).
 #include "nvo_kernels.h"
-#include "../../include/nerfvo_hip.h"
-
-#include <math.h>
+#include "tsdf_dev.h"
 
 namespace {
 
@@ -112,64 +109,16 @@ __global__ void __launch_bounds__(kBlock) k_tsdf_blocks_integrate(const nvo_tsdf
             const float px = a.lower_x + (float)i * a.voxel_size;
             const float py = a.lower_y + (float)j * a.voxel_size;
             const float pz = a.lower_z + (float)k * a.voxel_size;
-            bool touched = false;
-            float t = 0.f, w = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
-            for (uint32_t f = 0; f < a.K; ++f) {
-                if (!((live >> f) & 1u)) continue;
-                const float* c = cam + 16 * f;
-                const float zc = c[8] * px + c[9] * py + c[10] * pz + c[11];
-                if (zc <= 0.f) continue;
-                const float xc = c[0] * px + c[1] * py + c[2] * pz + c[3];
-                const float yc = c[4] * px + c[5] * py + c[6] * pz + c[7];
-                const float u = c[12] * xc / zc + c[14], v = c[13] * yc / zc + c[15];
-                const float ui = floorf(u + 0.5f), vi = floorf(v + 0.5f);
-                if (!(ui >= 0.f && ui < fW && vi >= 0.f && vi < fH)) continue;  // a NaN fails
-                const size_t pix = ((size_t)f * a.H + (uint32_t)vi) * a.W + (uint32_t)ui;
-                const float d = a.depth[pix];
-                if (!(d > 0.f && d <= a.depth_max)) continue;  // a NaN fails
-                const float sdf = d - zc;
-                if (sdf < -a.trunc) continue;
-                if (!touched) {
-                    t = a.tsdf[idx];
-                    w = a.weight[idx];
-                    cr = a.color[cidx];
-                    cg = a.color[cidx + kBlockVoxels];
-                    cb = a.color[cidx + 2 * kBlockVoxels];
-                    touched = true;
-                }
-                const float s = fminf(sdf, a.trunc) / a.trunc;
-                const uint8_t* p = a.rgb + 3 * pix;
-                const float w1 = w + 1.f;
-                t = (w * t + s) / w1;
-                cr = (w * cr + (float)p[0]) / w1;
-                cg = (w * cg + (float)p[1]) / w1;
-                cb = (w * cb + (float)p[2]) / w1;
-                w = w1;
-            }
-            if (touched) {
-                a.tsdf[idx] = t;
-                a.weight[idx] = w;
-                a.color[cidx] = cr;
-                a.color[cidx + kBlockVoxels] = cg;
-                a.color[cidx + 2 * kBlockVoxels] = cb;
-            }
+            tsdf_fuse_voxel(cam, a.K, live, a.H, a.W, fW, fH, a.depth, a.rgb, a.trunc, a.depth_max, px, py, pz, a.tsdf,
+                            a.weight, a.color, idx, cidx, kBlockVoxels);
         }
     }
 }
 
 int blocks_check(const nvo_tsdf_blocks_args& a, const char* what, uint64_t* n_table) {
     NVO_REQUIRE(a.frames && a.depth, "%s: NULL frames or depth", what);
-    NVO_REQUIRE(a.tbx >= 1 && a.tby >= 1 && a.tbz >= 1 && a.tbx <= NVO_TSDF_BLOCKS_MAX_TABLE && a.tby <= NVO_TSDF_BLOCKS_MAX_TABLE &&
-                    a.tbz <= NVO_TSDF_BLOCKS_MAX_TABLE && (uint64_t)a.tbx * a.tby <= NVO_TSDF_BLOCKS_MAX_TABLE &&
-                    (uint64_t)a.tbx * a.tby * a.tbz <= NVO_TSDF_BLOCKS_MAX_TABLE,
-                "%s: block table %u x %u x %u must have between 1 and 2^26 entries", what, a.tbx, a.tby, a.tbz);
-    NVO_REQUIRE(a.K >= 1 && a.K <= kMaxFrames, "%s: %u frames per launch not in 1..%u", what, a.K, kMaxFrames);
-    NVO_REQUIRE(a.H >= 1 && a.W >= 1 && a.H <= (1u << 16) && a.W <= (1u << 16), "%s: frame size %u x %u not in 1..65536", what, a.W,
-                a.H);
-    NVO_REQUIRE(a.voxel_size > 0.f && a.voxel_size < INFINITY && a.trunc > 0.f && a.trunc < INFINITY,
-                "%s: voxel_size %g and trunc %g must be positive and finite", what, (double)a.voxel_size, (double)a.trunc);
-    *n_table = (uint64_t)a.tbx * a.tby * a.tbz;
-    return NVO_OK;
+    if (int rc = tsdf_table_check(what, a.tbx, a.tby, a.tbz, n_table)) return rc;
+    return tsdf_frames_check(what, a.K, a.H, a.W, a.voxel_size, a.trunc);
 }
 
 }  // namespace

@@ -64,23 +64,55 @@ def frustum_bounds(depths, camera_to_world, intrinsics, depth_max: float = DEPTH
     return lower, upper
 
 
+def _parse_box(name, lower, upper, voxel_size, trunc_voxels, depth_max):
+    """(lower, upper) of a volume's box as float64 [3]; a ValueError unless the box and the three settings make sense."""
+    lo, hi = (np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=np.float64).reshape(3) for x in (lower, upper))
+    if not (voxel_size > 0 and trunc_voxels > 0 and depth_max > 0):
+        raise ValueError(f"{name}: voxel_size, trunc_voxels and depth_max must be positive")
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
+        raise ValueError(f"{name}: bad box {lo.tolist()} .. {hi.tolist()}")
+    return lo, hi
+
+
+def lattice_dims(lo, hi, voxel_size: float) -> tuple:
+    """Samples per axis of the lattice over [lo, hi]: ``lo + i * voxel_size`` up to the first one at or beyond hi."""
+    return tuple(int(math.ceil((h - l) / voxel_size - 1e-6)) + 1 for l, h in zip(lo, hi))
+
+
+def _pose(m, name, n, what):
+    m = torch.as_tensor(m)
+    if m.dim() != 3 or m.shape[0] != n or tuple(m.shape[1:]) not in ((4, 4), (3, 4)):
+        raise ValueError(f"{what}: {name} [N,4,4] expected, got {tuple(m.shape)}")
+    return m
+
+
+def _frame_table(world_to_camera, intrinsics, n, device, what):
+    """The kernels' frame table, float32 [N, 16]: world->camera 3x4 row-major, then fx fy cx cy."""
+    w2c = _pose(world_to_camera, "world_to_camera", n, what).to(device=device, dtype=torch.float32)
+    intr = torch.as_tensor(intrinsics, dtype=torch.float32).to(device)
+    intr = intr.expand(n, 4) if intr.dim() == 1 else intr
+    if tuple(intr.shape) != (n, 4):
+        raise ValueError(f"{what}: intrinsics (fx, fy, cx, cy) or [N,4] expected, got {tuple(intr.shape)}")
+    return torch.cat([w2c[:, :3, :4].reshape(n, 12), intr], dim=1).contiguous()
+
+
+def _check_frames_per_launch(frames_per_launch) -> int:
+    if not 1 <= int(frames_per_launch) <= _lib.TSDF_MAX_FRAMES:
+        raise ValueError(f"frames_per_launch must be in 1..{_lib.TSDF_MAX_FRAMES}")
+    return int(frames_per_launch)
+
+
 class TSDFVolume:
     """Dense truncated-signed-distance volume over [lower, upper]: voxel (i, j, k) samples ``lower + (i, j, k) * voxel_size``
     (no half-voxel offset).  ``tsdf`` / ``weight`` float32 [nx, ny, nz], ``color`` float32 [3, nx, ny, nz] (0..255)."""
 
     def __init__(self, lower, upper, voxel_size: float = VOXEL_SIZE, trunc_voxels: float = TRUNC_VOXELS,
                  depth_max: float = DEPTH_TRUNCATION, device="cuda", max_voxels: int = 2 ** 29) -> None:
-        lo = np.asarray(lower.detach().cpu().numpy() if torch.is_tensor(lower) else lower, dtype=np.float64).reshape(3)
-        hi = np.asarray(upper.detach().cpu().numpy() if torch.is_tensor(upper) else upper, dtype=np.float64).reshape(3)
-        if not (voxel_size > 0 and trunc_voxels > 0 and depth_max > 0):
-            raise ValueError("TSDFVolume: voxel_size, trunc_voxels and depth_max must be positive")
-        if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
-            raise ValueError(f"TSDFVolume: bad box {lo.tolist()} .. {hi.tolist()}")
+        lo, hi = _parse_box("TSDFVolume", lower, upper, voxel_size, trunc_voxels, depth_max)
         self.voxel_size = float(voxel_size)
         self.trunc = float(trunc_voxels) * self.voxel_size
         self.depth_max = float(depth_max)
-        # samples lower + i * voxel_size up to the first one at or beyond upper
-        self.dims = tuple(int(math.ceil((h - l) / self.voxel_size - 1e-6)) + 1 for l, h in zip(lo, hi))
+        self.dims = lattice_dims(lo, hi, self.voxel_size)
         n = self.dims[0] * self.dims[1] * self.dims[2]
         if n > max_voxels or n >= 2 ** 31:
             raise ValueError(
@@ -104,8 +136,7 @@ class TSDFVolume:
         into launches of at most ``frames_per_launch``; the result does not depend on the cut."""
         if not (self.tsdf.is_cuda and depth.is_cuda and rgb.is_cuda):
             raise RuntimeError("TSDFVolume.integrate: the volume and the frames must be on the GPU -- no CPU fallback")
-        if not 1 <= int(frames_per_launch) <= _lib.TSDF_MAX_FRAMES:
-            raise ValueError(f"frames_per_launch must be in 1..{_lib.TSDF_MAX_FRAMES}")
+        fpl = _check_frames_per_launch(frames_per_launch)
         if depth.dim() != 3 or rgb.shape != depth.shape + (3,) or rgb.dtype != torch.uint8:
             raise ValueError(f"integrate: depth [N,H,W] float and rgb [N,H,W,3] uint8 expected, got {tuple(depth.shape)} {depth.dtype} "
                              f"and {tuple(rgb.shape)} {rgb.dtype}")
@@ -113,17 +144,12 @@ class TSDFVolume:
         n, h, w = depth.shape
         depth = depth.to(device=dev, dtype=torch.float32).contiguous()
         rgb = rgb.to(device=dev).contiguous()
-        w2c = torch.as_tensor(world_to_camera).to(device=dev, dtype=torch.float32)
-        if w2c.shape[0] != n or tuple(w2c.shape[1:]) not in ((4, 4), (3, 4)):
-            raise ValueError(f"integrate: world_to_camera [N,4,4] expected, got {tuple(w2c.shape)}")
-        intr = torch.as_tensor(intrinsics, dtype=torch.float32).to(dev)
-        intr = intr.expand(n, 4) if intr.dim() == 1 else intr
-        table = torch.cat([w2c[:, :3, :4].reshape(n, 12), intr.reshape(n, 4)], dim=1).contiguous()  # [N, 16]
+        table = _frame_table(world_to_camera, intrinsics, n, dev, "integrate")
         lib = _lib.lib()
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         nx, ny, nz = self.dims
-        for lo in range(0, n, int(frames_per_launch)):
-            k = min(int(frames_per_launch), n - lo)
+        for lo in range(0, n, fpl):
+            k = min(fpl, n - lo)
             args = _lib.TsdfArgs(
                 tsdf=self.tsdf.data_ptr(), weight=self.weight.data_ptr(), color=self.color.data_ptr(),
                 frames=table[lo:].data_ptr(), depth=depth[lo:].data_ptr(), rgb=rgb[lo:].data_ptr(),
@@ -181,8 +207,7 @@ def block_table_dims(lower, upper, voxel_size: float = VOXEL_SIZE) -> tuple:
     beyond 2^26 entries."""
     lo = np.asarray(lower, dtype=np.float64).reshape(3)
     hi = np.asarray(upper, dtype=np.float64).reshape(3)
-    dims = [int(math.ceil((h - l) / voxel_size - 1e-6)) + 1 for l, h in zip(lo, hi)]
-    tb = tuple(-(-d // BLOCK) for d in dims)
+    tb = tuple(-(-d // BLOCK) for d in lattice_dims(lo, hi, voxel_size))
     n = tb[0] * tb[1] * tb[2]
     if n > _lib.TSDF_BLOCKS_MAX_TABLE:
         raise ValueError(
@@ -204,12 +229,7 @@ class TSDFBlockVolume:
 
     def __init__(self, lower, upper, voxel_size: float = VOXEL_SIZE, trunc_voxels: float = TRUNC_VOXELS,
                  depth_max: float = DEPTH_TRUNCATION, device="cuda", block_count: int = BLOCK_COUNT) -> None:
-        lo = np.asarray(lower.detach().cpu().numpy() if torch.is_tensor(lower) else lower, dtype=np.float64).reshape(3)
-        hi = np.asarray(upper.detach().cpu().numpy() if torch.is_tensor(upper) else upper, dtype=np.float64).reshape(3)
-        if not (voxel_size > 0 and trunc_voxels > 0 and depth_max > 0):
-            raise ValueError("TSDFBlockVolume: voxel_size, trunc_voxels and depth_max must be positive")
-        if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
-            raise ValueError(f"TSDFBlockVolume: bad box {lo.tolist()} .. {hi.tolist()}")
+        lo, hi = _parse_box("TSDFBlockVolume", lower, upper, voxel_size, trunc_voxels, depth_max)
         if not 1 <= int(block_count) <= _lib.TSDF_BLOCKS_MAX_ALLOCATED:
             raise ValueError(f"TSDFBlockVolume: block_count {block_count} not in 1..{_lib.TSDF_BLOCKS_MAX_ALLOCATED} "
                              "(block id * 512 + local index must stay below 2^31)")
@@ -284,33 +304,21 @@ class TSDFBlockVolume:
         n = depth.shape[0]
         depth = depth.to(device=dev, dtype=torch.float32).contiguous()
 
-        def pose(m, name):
-            m = torch.as_tensor(m)
-            if m.dim() != 3 or m.shape[0] != n or tuple(m.shape[1:]) not in ((4, 4), (3, 4)):
-                raise ValueError(f"{what}: {name} [N,4,4] expected, got {tuple(m.shape)}")
-            return m
+        def inverse(m):  # of the float32 matrices, in float64, rounded once
+            full = torch.eye(4, dtype=torch.float64, device=dev).repeat(n, 1, 1)
+            full[:, :3, :4] = m[:, :3, :4].double()
+            return torch.linalg.inv(full).float()
 
         if world_to_camera is None and camera_to_world is None:
             raise ValueError(f"{what}: world_to_camera or camera_to_world is needed")
-        if camera_to_world is None:  # the float32 matrix the touch rule maps with: the float64 inverse, rounded once
-            w2c = pose(world_to_camera, "world_to_camera").to(device=dev, dtype=torch.float32)
-            full = torch.eye(4, dtype=torch.float64, device=dev).repeat(n, 1, 1)
-            full[:, :3, :4] = w2c[:, :3, :4].double()
-            c2w = torch.linalg.inv(full).float()
+        if camera_to_world is None:  # the float32 matrix the touch rule maps with
+            c2w = inverse(_pose(world_to_camera, "world_to_camera", n, what).to(device=dev, dtype=torch.float32))
         else:
-            c2w = pose(camera_to_world, "camera_to_world").to(device=dev, dtype=torch.float32)
+            c2w = _pose(camera_to_world, "camera_to_world", n, what).to(device=dev, dtype=torch.float32)
             if world_to_camera is None:
-                full = torch.eye(4, dtype=torch.float64, device=dev).repeat(n, 1, 1)
-                full[:, :3, :4] = c2w[:, :3, :4].double()
-                w2c = torch.linalg.inv(full).float()
-            else:
-                w2c = pose(world_to_camera, "world_to_camera").to(device=dev, dtype=torch.float32)
-        intr = torch.as_tensor(intrinsics, dtype=torch.float32).to(dev)
-        intr = intr.expand(n, 4) if intr.dim() == 1 else intr
-        if tuple(intr.shape) != (n, 4):
-            raise ValueError(f"{what}: intrinsics (fx, fy, cx, cy) or [N,4] expected, got {tuple(intr.shape)}")
-        frames = torch.cat([w2c[:, :3, :4].reshape(n, 12), intr.reshape(n, 4)], dim=1).contiguous()  # [N, 16]
-        k_pix = (0.5 * torch.sqrt(1.0 / intr[:, 0].double() ** 2 + 1.0 / intr[:, 1].double() ** 2)).float()
+                world_to_camera = inverse(c2w)
+        frames = _frame_table(world_to_camera, intrinsics, n, dev, what)
+        k_pix = (0.5 * torch.sqrt(1.0 / frames[:, 12].double() ** 2 + 1.0 / frames[:, 13].double() ** 2)).float()
         touch = torch.cat([c2w[:, :3, :4].reshape(n, 12), k_pix[:, None], torch.zeros(n, 3, device=dev)], dim=1).contiguous()
         return depth, frames, touch
 
@@ -333,12 +341,6 @@ class TSDFBlockVolume:
         mask = marks[index]
         marks[index] = 0
         return index, mask
-
-    @staticmethod
-    def _check_launch(frames_per_launch):
-        if not 1 <= int(frames_per_launch) <= _lib.TSDF_MAX_FRAMES:
-            raise ValueError(f"frames_per_launch must be in 1..{_lib.TSDF_MAX_FRAMES}")
-        return int(frames_per_launch)
 
     @torch.no_grad()
     def touched_blocks(self, depth, camera_to_world, intrinsics) -> list:
@@ -373,7 +375,7 @@ class TSDFBlockVolume:
         allocated, and frame f goes into a block iff f touched it.  ``blocks='allocated'``: every frame goes into every
         block allocated so far (see ``allocate``), the dense rule restricted to those blocks.  Either way the result does
         not depend on ``frames_per_launch`` or on how the frames are split over calls."""
-        fpl = self._check_launch(frames_per_launch)
+        fpl = _check_frames_per_launch(frames_per_launch)
         if blocks not in ("touched", "allocated"):
             raise ValueError(f"integrate: blocks must be 'touched' or 'allocated', got {blocks!r}")
         if not (torch.is_tensor(rgb) and torch.is_tensor(depth) and depth.dim() == 3 and rgb.shape == depth.shape + (3,)
