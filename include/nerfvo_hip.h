@@ -1329,6 +1329,67 @@ uint32_t nvo_m2d_depth_chunks(uint32_t H, uint32_t W);
 uint64_t nvo_m2d_depth_scratch_bytes(uint32_t F, uint32_t H, uint32_t W);
 int nvo_m2d_depth(nvo_stream_t stream, const nvo_m2d_depth_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * O. LPIPS v0.1 with AlexNet features (csrc/lpips.hip): the eleventh column of metrics_2d_*.csv.  DESIGN.md section 17
+ *    states the rule; tests/helpers/lpips_oracle.py restates it in float64.  All images and maps are NCHW float32 except
+ *    the uint8 ingest.  fp32 operands and fp32 accumulation throughout, no atomics: a frame's values are bitwise the same
+ *    on every run and whatever other frames share the launch.
+ *      nvo_lpips_conv   out[f][m][oy][ox] = max(0, bias[m] + sum_k w[k][m] * patch[k]), k = (ci * ksize + ky) * ksize + kx
+ *                       ascending, as one fp32 fma chain from 0 (the matrix instruction), the bias added last.  Zero
+ *                       padding: a tap outside the image contributes 0.  `weights` is pre-packed k-major, [Kpad][Cout] with
+ *                       Kpad = nvo_lpips_conv_kpad(Cin * ksize * ksize) and zero rows past K.  (ksize, stride) is one of
+ *                       (11, 4), (5, 1), (3, 1); pad < ksize; Cout a multiple of NVO_LPIPS_TILE_M; F Ho Wo < 2^31.
+ *                       ingest 0: x is float [F][Cin][H][W], taken as it is.
+ *                       ingest 1 and 2 feed conv1 only (Cin = 3, ksize = 11).
+ *                       ingest 1: every tap inside the image is (x - shift[ci]) / scale[ci] (the scaling layer).
+ *                       ingest 2: x is uint8 [F][H][W][3]; a tap is ((float(u) / 255) * 2 - 1) * 2 - 1 and then the
+ *                                 scaling layer, one correctly rounded fp32 operation each, in that order.
+ *      nvo_lpips_pool   max-pool 3 x 3, stride 2, no padding, floor: [planes][H][W] -> [planes][(H-3)/2+1][(W-3)/2+1].
+ *      nvo_lpips_head   per frame and pixel n0 = sqrtf(sum_c f0_c^2) + 1e-10f (c ascending), n1 likewise,
+ *                       d = sum_c lin[c] * (f0_c / n0 - f1_c / n1)^2 (c ascending), written to map[F][HW] when map is not
+ *                       NULL.  A frame's HW pixels are cut into chunks of NVO_LPIPS_HEAD_BLOCK; a chunk's values (0 past the
+ *                       end) fold in float64 as a binary tree (v[t] += v[t + s] for t < s, s = 128 .. 1), the chunks are
+ *                       added in ascending order, the sum is divided by HW and rounded to float: out[f] = that value, or
+ *                       out[f] + that value (one fp32 addition) with `accumulate`.  1 <= F <= 65535.
+ *                       scratch: nvo_lpips_head_scratch_bytes(F, C, HW) bytes, 0 meaning "too large"; written before read.
+ * ---------------------------------------------------------------------------------------------- */
+#define NVO_LPIPS_TILE_M 64
+#define NVO_LPIPS_TILE_N 128
+#define NVO_LPIPS_TILE_K 16
+#define NVO_LPIPS_HEAD_BLOCK 256
+typedef struct nvo_lpips_conv_args {
+    const void* x;               /* float [F][Cin][H][W], or uint8 [F][H][W][3] with ingest 2 */
+    const float* weights;        /* [Kpad][Cout] */
+    const float* bias;           /* [Cout] */
+    float* out;                  /* [F][Cout][Ho][Wo] */
+    uint32_t F, Cin, H, W, Cout;
+    uint32_t ksize, stride, pad, Kpad;
+    int32_t ingest;
+    float shift[3], scale[3];    /* read with ingest 1 and 2 */
+} nvo_lpips_conv_args;
+uint32_t nvo_lpips_conv_kpad(uint32_t K);
+int nvo_lpips_conv(nvo_stream_t stream, const nvo_lpips_conv_args* args);
+
+typedef struct nvo_lpips_pool_args {
+    const float* x;              /* [planes][H][W] */
+    float* out;                  /* [planes][(H-3)/2+1][(W-3)/2+1] */
+    uint32_t planes, H, W;
+} nvo_lpips_pool_args;
+int nvo_lpips_pool(nvo_stream_t stream, const nvo_lpips_pool_args* args);
+
+typedef struct nvo_lpips_head_args {
+    const float* f0;             /* [F][C][HW] */
+    const float* f1;
+    const float* lin;            /* [C] */
+    float* map;                  /* [F][HW] or NULL */
+    void* scratch;               /* nvo_lpips_head_scratch_bytes(F, C, HW), 8-byte aligned */
+    float* out;                  /* [F] */
+    uint32_t F, C, HW;
+    int32_t accumulate;
+} nvo_lpips_head_args;
+uint64_t nvo_lpips_head_scratch_bytes(uint32_t F, uint32_t C, uint32_t HW);
+int nvo_lpips_head(nvo_stream_t stream, const nvo_lpips_head_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -264,6 +264,30 @@ M2D_COLOR_WORDS = 3    # NVO_M2D_COLOR_WORDS
 M2D_DEPTH_WORDS = 9    # NVO_M2D_DEPTH_WORDS
 
 
+class LpipsConvArgs(C.Structure):
+    """mirror of nvo_lpips_conv_args"""
+    _fields_ = [("x", _p), ("weights", _p), ("bias", _p), ("out", _p), ("F", _u32), ("Cin", _u32), ("H", _u32), ("W", _u32),
+                ("Cout", _u32), ("ksize", _u32), ("stride", _u32), ("pad", _u32), ("Kpad", _u32), ("ingest", _i32),
+                ("shift", _f * 3), ("scale", _f * 3)]
+
+
+class LpipsPoolArgs(C.Structure):
+    """mirror of nvo_lpips_pool_args"""
+    _fields_ = [("x", _p), ("out", _p), ("planes", _u32), ("H", _u32), ("W", _u32)]
+
+
+class LpipsHeadArgs(C.Structure):
+    """mirror of nvo_lpips_head_args"""
+    _fields_ = [("f0", _p), ("f1", _p), ("lin", _p), ("map", _p), ("scratch", _p), ("out", _p), ("F", _u32), ("C", _u32),
+                ("HW", _u32), ("accumulate", _i32)]
+
+
+LPIPS_TILE_M = 64        # NVO_LPIPS_TILE_M
+LPIPS_TILE_N = 128       # NVO_LPIPS_TILE_N
+LPIPS_TILE_K = 16        # NVO_LPIPS_TILE_K
+LPIPS_HEAD_BLOCK = 256   # NVO_LPIPS_HEAD_BLOCK
+
+
 _SIGNATURES = {
     "nvo_last_error": (C.c_char_p, []),
     "nvo_version": (_int, []),
@@ -377,6 +401,12 @@ _SIGNATURES = {
     "nvo_m2d_depth_chunks": (_u32, [_u32, _u32]),
     "nvo_m2d_depth_scratch_bytes": (_u64, [_u32, _u32, _u32]),
     "nvo_m2d_depth": (_int, [_p, C.POINTER(M2dDepthArgs)]),
+    # group O
+    "nvo_lpips_conv_kpad": (_u32, [_u32]),
+    "nvo_lpips_conv": (_int, [_p, C.POINTER(LpipsConvArgs)]),
+    "nvo_lpips_pool": (_int, [_p, C.POINTER(LpipsPoolArgs)]),
+    "nvo_lpips_head_scratch_bytes": (_u64, [_u32, _u32, _u32]),
+    "nvo_lpips_head": (_int, [_p, C.POINTER(LpipsHeadArgs)]),
     # group E
     "nvo_adam_step": (_int, [_p, C.POINTER(AdamArgs), _u32, C.POINTER(AdamGroup), C.POINTER(AdamTail)]),
     "nvo_opt_commit": (_int, [_p, C.POINTER(OptCommitArgs), C.POINTER(StepScalars)]),

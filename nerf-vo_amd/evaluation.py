@@ -10,8 +10,9 @@ Mirrors the behaviour of the reference's
   * ``Evaluator.calculate_metrics_2d`` (/root/reference/evaluation/evaluator.py:88-146),
 over ``nerf_vo_amd.mapping.renderer.NeRFRenderer`` objects.  Images are written with PIL (JPEG quality 95 is
 OpenCV's ``imwrite`` default; 16-bit PNG depth) because OpenCV is not part of this image.  LPIPS needs
-pretrained AlexNet weights that cannot be fetched here: ``lpips_loss`` is an optional callable and the
-``lpips`` column is omitted without it.
+pretrained AlexNet weights that are not shipped and never fetched: ``lpips_loss`` is an optional callable --
+``nerf_vo_amd.lpips.LPIPS.from_files(...)`` for the network in HIP, or any other -- and the ``lpips`` column is omitted
+without it.
 
 3-D (mesh) metrics: ``EvaluationRenderer.render_mesh`` produces the meshes (``source='frames'``: TSDF fusion of the rendered
 frames, tsdf.py; ``source='nerf'``: the model's density iso-surface cropped to the ground-truth mesh's box, meshing.py) and
@@ -405,7 +406,10 @@ class Evaluator2D:
                  frames_per_launch: int = 8) -> None:
         """``device``: None computes every frame on the host (the functions above); a CUDA device uploads the decoded
         frames ``frames_per_launch`` at a time and computes the same columns there (metrics2d.py, csrc/metrics2d.hip):
-        ``psnr`` is equal, the others agree to the bounds of DESIGN.md section 16.  ``lpips_loss`` stays on the host."""
+        ``psnr`` is equal, the others agree to the bounds of DESIGN.md section 16.  ``lpips_loss``: a
+        ``nerf_vo_amd.lpips.LPIPS`` model computes the ``lpips`` column on the device, from the batch already uploaded for
+        the colour metrics (host path: frame by frame through the model, same values); any other callable is fed on the
+        host, frame by frame."""
         self.dataset = dataset
         self.keyframes = list(keyframes)
         self.dir_prediction = dir_prediction
@@ -432,6 +436,9 @@ class Evaluator2D:
         def to_tensor(img):
             return torch.from_numpy(np.ascontiguousarray(img.transpose(2, 0, 1))).unsqueeze(0).float().div(255.0) * 2 - 1
 
+        from .lpips import LPIPS
+
+        lpips_model = self.lpips_loss if isinstance(self.lpips_loss, LPIPS) else None
         frames = [(depth_array(dg), depth_array(dp), np.asarray(cg), np.asarray(cp))
                   for dg, dp, cg, cp in zip(depths_gt, depths_pred, colors_gt, colors_pred)]
         rows, lo = [], 0
@@ -441,10 +448,10 @@ class Evaluator2D:
                 hi += 1
             d_gt, d_pred, c_gt, c_pred = (list(column) for column in zip(*frames[lo:hi]))
             depth_rows = metrics2d.depth_metrics(upload(d_gt), upload(d_pred))
-            color_rows = metrics2d.color_metrics(upload(c_gt), upload(c_pred))
+            color_rows = metrics2d.color_metrics(upload(c_gt), upload(c_pred), lpips=lpips_model)
             for k, (depth_row, color_row) in enumerate(zip(depth_rows, color_rows)):
                 row = {**depth_row, **color_row}
-                if self.lpips_loss is not None:  # on the host, fed as calculate_color_metrics_2d feeds it
+                if self.lpips_loss is not None and lpips_model is None:  # on the host, fed as calculate_color_metrics_2d feeds it
                     row["lpips"] = float(self.lpips_loss(to_tensor(c_gt[k]) * 2 - 1, to_tensor(c_pred[k]) * 2 - 1))
                 rows.append(row)
             lo = hi

@@ -91,10 +91,11 @@ def mssim_of_sums(sums, n_pixels: int) -> float:
     return sum(int(s) for s in sums) / (4294967296 * 3 * n_pixels)
 
 
-def color_metrics(gt: torch.Tensor, pred: torch.Tensor, float_psnr: bool = False):
-    """``calculate_color_metrics_2d`` (without LPIPS) of uint8 frames on the device: ``{"psnr", "mssim"}`` for one
-    [H, W, 3] pair, a list of such dicts for a batch [F, H, W, 3].  ``float_psnr``: also ``"psnr_float"``, the conventional
-    PSNR of ``calculate_psnr_float``."""
+def color_metrics(gt: torch.Tensor, pred: torch.Tensor, float_psnr: bool = False, lpips=None):
+    """``calculate_color_metrics_2d`` of uint8 frames on the device: ``{"psnr", "mssim"}`` for one [H, W, 3] pair, a list
+    of such dicts for a batch [F, H, W, 3].  ``float_psnr``: also ``"psnr_float"``, the conventional PSNR of
+    ``calculate_psnr_float``.  ``lpips``: a ``nerf_vo_amd.lpips.LPIPS`` model; its ``lpips_uint8`` of the same batch is
+    added as ``"lpips"``."""
     single = gt.ndim == 3
     if single:
         gt, pred = gt[None], pred[None]
@@ -102,11 +103,14 @@ def color_metrics(gt: torch.Tensor, pred: torch.Tensor, float_psnr: bool = False
         raise ValueError(f"color_metrics: uint8 [H,W,3] or [F,H,W,3] frames, got {gt.dtype}")
     table = color_accumulators(gt, pred).cpu().tolist()
     n = int(gt.shape[1]) * int(gt.shape[2])
+    distances = lpips.lpips_uint8(gt, pred) if lpips is not None else None
     rows = []
-    for frame in table:
+    for k, frame in enumerate(table):
         row = {"psnr": _psnr_of_sums([ch[0] for ch in frame], n), "mssim": mssim_of_sums([ch[2] for ch in frame], n)}
         if float_psnr:
             row["psnr_float"] = _psnr_of_sums([ch[1] for ch in frame], n)
+        if distances is not None:
+            row["lpips"] = distances[k]
         rows.append(row)
     return rows[0] if single else rows
 

@@ -124,8 +124,10 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
         camera_optimizer_mode=None, pose_noise=None, deterministic=False, seed=42, dynamic_loss_scale=None, out_dir=None,
         quiet=True, keyframe_views=True, method="nerfstudio", scene_scale=None, mesh=False, metrics_3d=False,
         mesh_nerf=False, pointcloud=False, pointcloud_points=33554432, poisson_depth=None, mesh_nerf_points=None,
-        mesh_nerf_attributes=False, mesh_volume="dense", metrics_device="cpu"):
-    """``metrics_device``: 'cpu' computes metrics_2d_*.csv on the host, 'cuda' on the GPU (``Evaluator2D(device=...)``,
+        mesh_nerf_attributes=False, mesh_volume="dense", metrics_device="cpu", lpips_weights=None):
+    """``lpips_weights``: weight files of AlexNet and of the LPIPS linear layers (``nerf_vo_amd.lpips.LPIPS.from_files``);
+    with them metrics_2d_*.csv has the reference's ``lpips`` column, without them it is left out as before.
+    ``metrics_device``: 'cpu' computes metrics_2d_*.csv on the host, 'cuda' on the GPU (``Evaluator2D(device=...)``,
     nerf_vo_amd/metrics2d.py).  The trajectory table results/metrics_trajectory.csv (run.py:78) is always written: its
     ``keyframes_mapping`` row scores the exported (optimised) keyframe poses, its ``keyframes_tracking`` row the poses as
     ingested, written with the same translation scaling -- the place the reference's tracker output takes.
@@ -271,7 +273,13 @@ def run(keyframes=48, height=120, width=160, iterations=1500, frame_stride=2, ev
 
     m_traj = {row["trajectory"]: {k: float(v) for k, v in row.items() if k != "trajectory"}
               for row in pd.read_csv(out_dir + "/results/metrics_trajectory.csv").to_dict("records")}
-    ev = Evaluator2D(ds, kf, args.dir_prediction, out_dir + "/results", device=None if metrics_device == "cpu" else dev)
+    lpips_loss = None
+    if lpips_weights:
+        from nerf_vo_amd.lpips import LPIPS
+
+        lpips_loss = LPIPS.from_files(*lpips_weights, device=dev)
+    ev = Evaluator2D(ds, kf, args.dir_prediction, out_dir + "/results", lpips_loss=lpips_loss,
+                     device=None if metrics_device == "cpu" else dev)
     m_eval = ev.calculate_metrics_2d(mode="evaluation_frames")
     m_kf = {}
     if keyframe_views:  # (every keyframe through JPEG / PNG files and the CPU metrics: seconds per hundred frames)
@@ -359,6 +367,8 @@ if __name__ == "__main__":
     ap.add_argument("--pointcloud-points", type=int, default=33554432, help="points of the cloud before outlier removal and crop")
     ap.add_argument("--metrics-device", default="cpu", choices=["cpu", "cuda"], help="where metrics_2d_*.csv is computed: the host "
                     "functions, or the HIP kernels of nerf_vo_amd/metrics2d.py on batches of uploaded frames")
+    ap.add_argument("--lpips-weights", nargs="+", default=None, metavar="FILE", help="AlexNet's and the LPIPS linear layers' weight "
+                    "files (one or two .pth state dicts; never fetched): adds the lpips column to metrics_2d_*.csv")
     a = ap.parse_args()
     run(a.keyframes, a.height, a.width, a.iterations, eval_frames=a.eval_frames, camera_optimizer_mode=a.camera_optimizer_mode,
         pose_noise=a.pose_noise, deterministic=a.deterministic, seed=a.seed, quiet=False,
@@ -366,4 +376,4 @@ if __name__ == "__main__":
         method=a.method, scene_scale=a.scene_scale, mesh=a.mesh, metrics_3d=a.metrics_3d, mesh_nerf=a.mesh_nerf,
         pointcloud=a.pointcloud, pointcloud_points=a.pointcloud_points, poisson_depth=a.poisson_depth,
         mesh_nerf_points=a.mesh_nerf_points, mesh_nerf_attributes=a.mesh_nerf_attributes, mesh_volume=a.mesh_volume,
-        metrics_device=a.metrics_device)
+        metrics_device=a.metrics_device, lpips_weights=a.lpips_weights)
