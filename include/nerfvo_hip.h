@@ -1390,6 +1390,82 @@ typedef struct nvo_lpips_head_args {
 uint64_t nvo_lpips_head_scratch_bytes(uint32_t F, uint32_t C, uint32_t HW);
 int nvo_lpips_head(nvo_stream_t stream, const nvo_lpips_head_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * P. Dense bundle adjustment over a window of keyframes (csrc/dense_ba.hip): poses, inverse depths and the marginal
+ *    depth variance the occupancy-grid mapper trains on.  DESIGN.md section 18 states the rule;
+ *    tests/helpers/dense_ba_oracle.py restates it in float64.  Poses are cam_T_world rows [tx ty tz qx qy qz qw] (unit
+ *    quaternion), tangent order (tau, phi), G <- Exp(xi) G.  Per-pixel arithmetic is fp32, one rounding per written
+ *    operation; sums over pixels fold in a fixed tree and then in float64; no atomics: every output is a function of
+ *    the inputs alone.
+ *
+ *    A PLAN holds the frame graph.  nvo_ba_plan_create validates every index on the host (0 <= ii, jj < K, ii != jj,
+ *    t0 < t1 <= K, sizes within one launch's range), derives kx = unique(ii) ascending and the list of edges by source
+ *    frame in edge order, and refuses anything else through nvo_last_error -- the kernels only ever see tables it built.
+ *    nvo_ba_plan_bind copies those tables into caller-owned device memory of nvo_ba_plan_bytes(plan) bytes (16-byte
+ *    aligned; tables first, scratch after) on `stream`; the launchers below run on a bound plan.  P = t1 - t0 free
+ *    poses, n = 6 P, HW = ht * wd, M edges, Kx = |kx|.
+ *
+ *      nvo_ba_reproject   coords[e][2][HW], valid[e][HW] (1 where z >= 0.25) of every edge.  Same device function as
+ *                         nvo_ba_accumulate; an edge's rows do not depend on the other edges of the launch.
+ *      nvo_ba_accumulate  B [n][n], v [n] (float64), C, wz, Q = 1 / (C + eta) [Kx][HW], Ei [P][6][HW], Ej [M][6][HW], and,
+ *                         when Ehat is not NULL, Ehat [Kx][P][6][HW]: row (s, a) = (kx[s] - t0 == a ? Ei[a] : 0) + the Ej of
+ *                         the edges kx[s] -> t0 + a in edge order.  A workgroup owns 256 pixels of one edge; its 90 block
+ *                         sums (upper triangles of J_i J_i' and J_j J_j', J_i J_j', r J_i, r J_j) reduce over the wave by
+ *                         DPP and over the four waves in order, and fold over tiles and edges in float64, edge order.
+ *      nvo_ba_schur       S = B + prior_weight I (first free pose's block) - sum_s Ehat_s diag(Q_s) Ehat_s',
+ *                         g = v - sum_s Ehat_s (Q_s o wz_s), float64 products and sums on v_mfma_f64_16x16x4_f64: per
+ *                         source frame and chunk of 1024 pixels one 16 x 16 tile per wave, pixels ascending; the partial
+ *                         tiles are subtracted in (s, chunk) order.
+ *      nvo_ba_solve       float64 Cholesky S = L L' in one workgroup, dx = S^-1 g, Linv = L^-1, for n <= NVO_BA_MAX_NATIVE_N.
+ *                         status[0] = 0, or 1 + the column whose pivot was not positive (L, Linv, dx are then undefined).
+ *      nvo_ba_update      when status[0] == 0: G_k <- Exp(dx_k) G_k in float64, quaternion renormalised, stored as float;
+ *                         d <- max(d + Q (wz - Ehat' dx), 0.001) on the kx frames (fp32).  Otherwise nothing is written.
+ *      nvo_ba_covariance  cov[kx[s]][p] = (Q + sum_c (Q sum_r Ehat_s[r][p] Mx[r][c])^2) / d^4, float64 sums, stored as
+ *                         float; rows of cov that are not in kx are not touched.
+ * ---------------------------------------------------------------------------------------------- */
+#define NVO_BA_MAX_NATIVE_N 192
+#define NVO_BA_TILE 256
+#define NVO_BA_SUMS 90
+#define NVO_BA_SCHUR_CHUNK 1024
+typedef struct nvo_ba_args {
+    float* poses;                /* [K][7]; written by nvo_ba_update */
+    float* disps;                /* [K][HW]; written by nvo_ba_update */
+    float intrinsics[4];         /* fx fy cx cy */
+    const float* target;         /* [M][2][HW] */
+    const float* weight;         /* [M][2][HW] */
+    const float* eta;            /* [Kx][HW] */
+    float* coords;               /* [M][2][HW] */
+    uint8_t* valid;              /* [M][HW] */
+    double* B;                   /* [n][n] */
+    double* v;                   /* [n] */
+    float* C;                    /* [Kx][HW] */
+    float* wz;                   /* [Kx][HW] */
+    float* Q;                    /* [Kx][HW] */
+    float* Ei;                   /* [P][6][HW] */
+    float* Ej;                   /* [M][6][HW] */
+    float* Ehat;                 /* [Kx][P][6][HW] */
+    double* S;                   /* [n][n] */
+    double* g;                   /* [n] */
+    double prior_weight;         /* 1 / sigma^2, or 0 */
+    const double* dx;            /* [n] */
+    const double* Mx;            /* [n][n] */
+    const int32_t* status;       /* [1], or NULL: proceed */
+    float* cov;                  /* [K][HW] */
+} nvo_ba_args;
+int nvo_ba_plan_create(const int64_t* ii, const int64_t* jj, uint32_t M, uint32_t K, uint32_t t0, uint32_t t1, uint32_t ht,
+                       uint32_t wd, void** plan);
+int nvo_ba_plan_destroy(void* plan);
+uint64_t nvo_ba_plan_bytes(const void* plan);
+uint32_t nvo_ba_plan_kx(const void* plan, int64_t* kx_out);   /* returns Kx; kx_out may be NULL */
+int nvo_ba_plan_bind(nvo_stream_t stream, void* plan, void* device_memory, uint64_t bytes);
+int nvo_ba_reproject(nvo_stream_t stream, const void* plan, const nvo_ba_args* args);
+int nvo_ba_accumulate(nvo_stream_t stream, const void* plan, const nvo_ba_args* args);
+int nvo_ba_schur(nvo_stream_t stream, const void* plan, const nvo_ba_args* args);
+int nvo_ba_solve(nvo_stream_t stream, uint32_t n, const double* S, const double* g, double* L, double* Linv, double* dx,
+                 int32_t* status);
+int nvo_ba_update(nvo_stream_t stream, const void* plan, const nvo_ba_args* args);
+int nvo_ba_covariance(nvo_stream_t stream, const void* plan, const nvo_ba_args* args);
+
 #ifdef __cplusplus
 }
 #endif

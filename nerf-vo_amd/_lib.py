@@ -288,6 +288,17 @@ LPIPS_TILE_K = 16        # NVO_LPIPS_TILE_K
 LPIPS_HEAD_BLOCK = 256   # NVO_LPIPS_HEAD_BLOCK
 
 
+class BaArgs(C.Structure):
+    """mirror of nvo_ba_args"""
+    _fields_ = [("poses", _p), ("disps", _p), ("intrinsics", _f * 4), ("target", _p), ("weight", _p), ("eta", _p),
+                ("coords", _p), ("valid", _p), ("B", _p), ("v", _p), ("C", _p), ("wz", _p), ("Q", _p), ("Ei", _p), ("Ej", _p),
+                ("Ehat", _p), ("S", _p), ("g", _p), ("prior_weight", C.c_double), ("dx", _p), ("Mx", _p), ("status", _p),
+                ("cov", _p)]
+
+
+BA_MAX_NATIVE_N = 192    # NVO_BA_MAX_NATIVE_N
+
+
 _SIGNATURES = {
     "nvo_last_error": (C.c_char_p, []),
     "nvo_version": (_int, []),
@@ -407,6 +418,18 @@ _SIGNATURES = {
     "nvo_lpips_pool": (_int, [_p, C.POINTER(LpipsPoolArgs)]),
     "nvo_lpips_head_scratch_bytes": (_u64, [_u32, _u32, _u32]),
     "nvo_lpips_head": (_int, [_p, C.POINTER(LpipsHeadArgs)]),
+    # group P
+    "nvo_ba_plan_create": (_int, [_p, _p, _u32, _u32, _u32, _u32, _u32, _u32, C.POINTER(_p)]),
+    "nvo_ba_plan_destroy": (_int, [_p]),
+    "nvo_ba_plan_bytes": (_u64, [_p]),
+    "nvo_ba_plan_kx": (_u32, [_p, _p]),
+    "nvo_ba_plan_bind": (_int, [_p, _p, _p, _u64]),
+    "nvo_ba_reproject": (_int, [_p, _p, C.POINTER(BaArgs)]),
+    "nvo_ba_accumulate": (_int, [_p, _p, C.POINTER(BaArgs)]),
+    "nvo_ba_schur": (_int, [_p, _p, C.POINTER(BaArgs)]),
+    "nvo_ba_solve": (_int, [_p, _u32, _p, _p, _p, _p, _p, _p]),
+    "nvo_ba_update": (_int, [_p, _p, C.POINTER(BaArgs)]),
+    "nvo_ba_covariance": (_int, [_p, _p, C.POINTER(BaArgs)]),
     # group E
     "nvo_adam_step": (_int, [_p, C.POINTER(AdamArgs), _u32, C.POINTER(AdamGroup), C.POINTER(AdamTail)]),
     "nvo_opt_commit": (_int, [_p, C.POINTER(OptCommitArgs), C.POINTER(StepScalars)]),
