@@ -551,8 +551,7 @@ int nvo_adam_step(nvo_stream_t stream, const nvo_adam_args* args, uint32_t n_gro
         gr.offset[k] = o;
         gr.n[k] = groups[i].n;
         gr.lr[k] = groups[i].lr;
-        gr.bias1[k] = 1.f - powf(a.beta1, (float)(groups[i].step ? groups[i].step : 1u));
-        gr.bias2_sqrt[k] = sqrtf(1.f - powf(a.beta2, (float)(groups[i].step ? groups[i].step : 1u)));
+        nvo_host_bias_pair(a.beta1, a.beta2, groups[i].step, &gr.bias1[k], &gr.bias2_sqrt[k]);
         gr.hyper_dev[k] = groups[i].hyper_dev;
         gr.bias_dev[k] = groups[i].bias_dev;
         gr.slot[k] = groups[i].flag_slot;

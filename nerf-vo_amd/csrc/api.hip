@@ -437,8 +437,7 @@ struct GridModule : nvo_module_s {
         d.eps = a->eps;
         if (!a->bias_dev) {  // as nvo_adam_step prices a host-side step count
             NVO_REQUIRE(a->step >= 1, "set_fused_adam: step counts from 1 (or pass bias_dev)");
-            d.bias1 = 1.f - powf(a->beta1, (float)a->step);
-            d.bias2_sqrt = sqrtf(1.f - powf(a->beta2, (float)a->step));
+            nvo_host_bias_pair(a->beta1, a->beta2, a->step, &d.bias1, &d.bias2_sqrt);
         }
         d.ema = a->ema ? a->ema + off : nullptr;
         d.ema_half = a->ema_half ? (char*)a->ema_half + 2 * off : nullptr;

@@ -185,6 +185,15 @@ __device__ __forceinline__ void nvo_adam_one(float& p, float& m, float& v, float
     const float denom = sqrtf(v) / h.bias2_sqrt + h.eps;
     p -= (h.lr / h.bias1) * (m / denom);
 }
+// Bias corrections of applied step `step` (>= 1) from a HOST step count: the double formula on the fp32 betas, rounded
+// once -- the words opt_commit_thread (adam.hip) leaves in bias_dev for that step, so a step priced from `step = t` and one
+// priced from a pair committed at t - 1 move the same bits.  (1.f - powf(beta, t) in fp32 put the update of t = 2 3.6e-6 of its
+// maximum off, where the whole fp32 chain of nvo_adam_one accounts for 6.4e-7: EXPERIMENTS.md section 26.)
+inline void nvo_host_bias_pair(float beta1, float beta2, uint32_t step, float* bias1, float* bias2_sqrt) {
+    const double t = (double)(step ? step : 1u);
+    *bias1 = (float)(1.0 - pow((double)beta1, t));
+    *bias2_sqrt = (float)sqrt(1.0 - pow((double)beta2, t));
+}
 __device__ __forceinline__ float2 nvo_ld16x2(uint32_t raw, bool bf) {
     if (bf) return make_float2(__uint_as_float(raw << 16), __uint_as_float(raw & 0xFFFF0000u));
     return make_float2((float)__builtin_bit_cast(_Float16, (nvo_h16)(raw & 0xFFFFu)),
